@@ -13,6 +13,12 @@ itself (view_parallel.launch_ranks).  Upstream gradients dL/dcolor, dL/dlanguage
 step is the rasterizer alone.  Inputs are resident in HBM before the timed region.
 
 value = frames (views) rendered fwd+bwd by all ranks / max over ranks of the timed wall time.
+
+A plain run sets up, warms up, times --steps steps and prints the result line (metric, value,
+unit, ms_per_step, dtype, config, ...); nothing else runs.  --dump-outputs DIR also writes what
+the last timed step computed (dump_outputs below).  Everything under here is measured only with
+--full, which fills the line's roofline, frame_roofline, phases, single_view and cpu_baseline
+entries (None / empty in a plain run):
 roofline: the dominant kernel (largest event-timed phase of one untimed all-phase step),
 algorithmic bytes per launch (the per-phase formulas below) / its mean launch time
 (hipEvents on the launch stream, recorded live over the timed region; only that phase carries
@@ -199,6 +205,57 @@ def _n_binning_batches(early, V):
     return len(cuts) + 1
 
 
+DUMP_SEED = 20240607
+DUMP_GRAD_BYTES = 28 << 20    # the gradient rows' share of the 64 MB a dump may take
+DUMP_RADII_ROWS = 1 << 21     # 8 MB
+DUMP_IMAGE_BYTES = 16 << 20   # the rendered views' share, per rank
+
+
+def dump_sample(n, keep, seed):
+    """Sorted indices of a fixed sample of `keep` out of n (all of them if n <= keep): the first
+    `keep` of a seeded CPU permutation, so the same arguments give the same sample in every run."""
+    if n <= keep:
+        return torch.arange(n)
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return torch.randperm(n, generator=g)[:keep].sort().values
+
+
+def dump_outputs(out_dir, bucket, images, rank, world):
+    """What a caller of the timed step receives, from the last timed step, as float32 .npy files:
+      grad_<field>.npy  the bucket's gradient sums over the step's views (means3D, scales, rotations,
+                        opacities, sh, language_feature, means2D), a seeded sample of Gaussian rows
+      radii_max.npy     the per-Gaussian radii MAX over the views (every row up to 2^21, else a sample)
+      color.npy, language.npy, depth.npy
+                        [views, channels, pixels]: the renders the loss callback was handed, this
+                        rank's views in order, a seeded sample of pixels (the same for every view)
+    The bucket is the same on every rank after the all-reduce, so rank 0 writes it; with more than
+    one rank the image files carry a _rank<r> suffix.  At most 64 MB in all (per rank)."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+
+    if rank == 0:
+        P = bucket.P
+        rows = dump_sample(P, max(1, DUMP_GRAD_BYTES // (4 * bucket.floats_per_gaussian)), DUMP_SEED)
+        rows = rows.to(bucket.flat.device)
+        for name, view in bucket.views.items():
+            if view is not None:
+                save("grad_" + name, view[rows])
+        if bucket.radii is not None:
+            save("radii_max", bucket.radii[dump_sample(P, DUMP_RADII_ROWS, DUMP_SEED + 1).to(bucket.radii.device)])
+    if images:
+        views = sorted(images)
+        chans = sum(t.shape[0] for t in images[views[0]] if t is not None)
+        npix = images[views[0]][0][0].numel()
+        pix = dump_sample(npix, max(1, DUMP_IMAGE_BYTES // (4 * chans * len(views))), DUMP_SEED + 2)
+        suffix = f"_rank{rank}" if world > 1 else ""
+        for i, name in enumerate(("color", "language", "depth")):
+            if images[views[0]][i] is not None and images[views[0]][i].shape[0] > 0:
+                dev = images[views[0]][i].device
+                save(name + suffix, torch.stack([images[v][i].flatten(1)[:, pix.to(dev)] for v in views]))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -209,6 +266,13 @@ def parse_args(argv=None):
     ap.add_argument("--channels", type=int, default=32)
     ap.add_argument("--width", type=int, default=1352)
     ap.add_argument("--height", type=int, default=1014)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline figure: the per-phase profile and roofline, "
+                         "the single-view figure and the CPU baselines (the options below that skip one of them "
+                         "apply to a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                         "(float32; seeded samples of the large arrays, see dump_outputs)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="oracle threads (0 = every core available to the process)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -312,7 +376,14 @@ def run(args):
     g = torch.Generator(device="cpu").manual_seed(123)
     gcol = (torch.randn(3, H, W, generator=g) * 1e-3).to(dev)
     glang = (torch.randn(C, H, W, generator=g) * 1e-3).to(dev)
-    render = native_view_renderer(scene, settings, lambda v, color, lang, depth: (gcol, glang, None),
+    captured = [None]                                      # --dump-outputs: {view: renders} of the last timed step
+
+    def upstream_grads(v, color, lang, depth):
+        if captured[0] is not None:                        # references only: no work on the device
+            captured[0][v] = (color, lang, depth)
+        return gcol, glang, None
+
+    render = native_view_renderer(scene, settings, upstream_grads,
                                   overlap=False if args.no_overlap else (True if args.pipeline == "side"
                                                                          else args.pipeline),
                                   early_views=args.early_views, composite_batch=not args.per_view_composite,
@@ -354,7 +425,8 @@ def run(args):
     # dominant kernel (the single-kernel phase with the most time; multi-kernel phases such as the
     # sorts cannot be matched to one rocprof kernel line)
     prof_all, dom = {}, None
-    if not args.no_profile:
+    profile = args.full and not args.no_profile
+    if profile:
         torch.cuda.synchronize(dev)
         _lib.profile_enable(True)
         step()
@@ -370,14 +442,21 @@ def run(args):
         dist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if args.dump_outputs and i == args.steps - 1:
+            captured[0] = {}
         step()
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    prof = _lib.profile_read() if not args.no_profile else {}
-    _lib.profile_enable(False)
+    prof = _lib.profile_read() if profile else {}
+    if profile:
+        _lib.profile_enable(False)
+    if args.dump_outputs:                                  # before anything else touches the bucket
+        images, captured[0] = captured[0], None
+        dump_outputs(args.dump_outputs, bucket, images, rank, world)
+        del images
     # every view's backward ran, timed (a batched launch serves a binning batch of views)
     if hasattr(render, "render_batch"):
         want = _n_binning_batches(args.early_views, V)
@@ -393,7 +472,7 @@ def run(args):
     value = frames / elapsed
 
     single = None
-    if args.single_view_steps > 0 and world == 1:   # configs[2] literally: one GPU
+    if args.full and args.single_view_steps > 0 and world == 1:   # configs[2] literally: one GPU
         # secondary figure: BASELINE configs[2] literally, one view at a time through the per-view
         # entry points (forward_native + backward_native, workspaces allocated per call), no batching
         v0 = dp.views[0]
@@ -416,6 +495,9 @@ def run(args):
 
     if rank == 0:
         Kmean = float(np.mean(Ks)) if Ks else 0.0
+        Pvis = Pany = roof = frame_roof = cpu = None       # measured by a --full run only
+        phases = {}
+    if rank == 0 and args.full:
         with torch.no_grad():
             vis_sum, any_vis = 0, torch.zeros(P, dtype=torch.bool, device=dev)
             for v in dp.views:
@@ -524,11 +606,13 @@ def run(args):
             if not args.no_configs0:
                 cpu["configs0"], gpu0 = configs0_leg(threads, dev)
                 cpu["configs0"]["gpu_frames_per_s"] = gpu0
+    if rank == 0:
         line = dict(
             metric="rasterizer fwd+bwd frames/sec @ 2M Gaussians, 1352x1014, 32-ch features",
             value=round(value, 3), unit="frames/s", n_gpus=world, ranks=pg_ranks, steps=args.steps, warmup=args.warmup,
             ms_per_step=round(elapsed / args.steps * 1e3, 3), higher_is_better=True, scaling="weak",
             vs_baseline=None, dtype="f32", data="synthetic",
+            full=bool(args.full), dumped_outputs=args.dump_outputs,
             precision=("fp32 per-pixel arithmetic (T, alpha, RGB, depth, the recurrences); the language "
                        "channel sums and the backward's per-Gaussian pixel sums on MFMA as bf16 hi/lo "
                        "splits, three products, fp32 accumulation (~2^-17 relative)"),

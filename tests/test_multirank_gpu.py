@@ -41,7 +41,7 @@ def test_bench_two_ranks_prints_one_line():
     """bench.py --gpus 2 at the headline size (2M, 1352x1014, C = 32, 8 views per rank): one JSON
     line from rank 0 with both ranks' 16 views counted and the process group's rank count."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--single-view-steps", "0"]
+           "--full", "--no-cpu-baseline", "--single-view-steps", "0"]   # --full: the line's roofline entry
     r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -6,7 +6,7 @@
 #
 # tasks
 #   tests      the -m gpu suite (PYTEST_ARGS: extra args / node ids, default the whole tests/ dir)
-#   bench      bench.py --steps ${STEPS:-20} --warmup 5, the full line with both CPU legs ($BENCH_ARGS)
+#   bench      bench.py --full --steps ${STEPS:-20} --warmup 5, the full line with both CPU legs ($BENCH_ARGS)
 #   prof       rocprofv3 --kernel-trace --stats of a 5-step bench, kernel_stats.csv + step_timeline.txt
 #   pmc        the PMC passes (one counter group each, kernel trace only) + pmc_summary / pmc_traffic.json
 #   mfma       matrix-core busy cycles over the headline bench and the deformation bench
@@ -49,12 +49,12 @@ for task in "$@"; do
       tail -3 "$O/gpu_tests.txt"
       [ $rc -ne 0 ] && { grep -E "^(FAILED|ERROR|E )" "$O/gpu_tests.txt" | head -30; exit $rc; } ;;
     bench)
-      timeout -k 10 400 python bench.py --steps ${STEPS:-20} --warmup 5 ${BENCH_ARGS:-} > "$O/bench.log" 2>&1 \
+      timeout -k 10 400 python bench.py --full --steps ${STEPS:-20} --warmup 5 ${BENCH_ARGS:-} > "$O/bench.log" 2>&1 \
           || { tail -5 "$O/bench.log"; fail bench; }
       grep '^{' "$O/bench.log" | tail -1 > "$O/bench.json"; head -c 700 "$O/bench.json"; echo ;;
     prof)
       timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run -- \
-          python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --single-view-steps 0 ${BENCH_ARGS:-} \
+          python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --single-view-steps 0 ${BENCH_ARGS:-} \
           > "$O/prof_bench.log" 2>&1 || { tail -5 "$O/prof_bench.log"; fail rocprof; }
       cp "$(find "$O/prof" -name '*kernel_stats.csv' | head -1)" "$O/kernel_stats.csv"
       python3 tools/step_timeline.py "$(find "$O/prof" -name '*kernel_trace.csv' | head -1)" > "$O/step_timeline.txt"
@@ -63,7 +63,7 @@ for task in "$@"; do
       rm -rf "$O/prof" ;;
     pmc)
       rm -rf "$O/pmc"; mkdir -p "$O/pmc"
-      pmc_passes "$O/pmc" 300 "--steps 1 --warmup 1 --no-cpu-baseline --no-profile --single-view-steps 0 ${BENCH_ARGS:-}" \
+      pmc_passes "$O/pmc" 300 "--full --steps 1 --warmup 1 --no-cpu-baseline --no-profile --single-view-steps 0 ${BENCH_ARGS:-}" \
           "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU" \
           "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU" \
           "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS" \
@@ -72,7 +72,7 @@ for task in "$@"; do
       head -30 "$O/pmc_summary.txt"; rm -rf "$O"/pmc/p*/ ;;
     mfma)
       for w in raster deform; do
-        if [ $w = raster ]; then cmd="bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-profile --single-view-steps 0"
+        if [ $w = raster ]; then cmd="bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-profile --single-view-steps 0"
         else cmd="tools/bench_deform.py --iters 2 --no-torch"; fi
         timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace \
             --output-format csv -d "$O/mfma_$w/p1" -o run -- python3 $cmd > "$O/mfma_$w.log" 2>&1 \
@@ -81,7 +81,7 @@ for task in "$@"; do
       done ;;
     stall)
       rm -rf "$O/stall"; mkdir -p "$O/stall"
-      pmc_passes "$O/stall" 180 "--steps 1 --warmup 1 --no-cpu-baseline --no-profile --single-view-steps 0 ${BENCH_ARGS:-}" \
+      pmc_passes "$O/stall" 180 "--full --steps 1 --warmup 1 --no-cpu-baseline --no-profile --single-view-steps 0 ${BENCH_ARGS:-}" \
           "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_WAIT_INST_LDS" \
           "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_MFMA SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC"
       python3 tools/pmc_summary.py "$O/stall" > "$O/stall_summary.txt" 2>&1
@@ -91,7 +91,7 @@ for task in "$@"; do
       for i in $(seq 1 ${REPS:-2}); do
         for j in "${!SETS[@]}"; do
           read -ra f <<< "${SETS[$j]}"
-          LSR_LIBRARY=$(lib_of "${f[0]}") timeout -k 10 300 python bench.py --steps ${STEPS:-20} --warmup 2 \
+          LSR_LIBRARY=$(lib_of "${f[0]}") timeout -k 10 300 python bench.py --full --steps ${STEPS:-20} --warmup 2 \
               --no-cpu-baseline --single-view-steps 0 "${f[@]:1}" > "$O/ab_s${j}_$i.log" 2>&1 \
               || { tail -5 "$O/ab_s${j}_$i.log"; fail "ab ${SETS[$j]}"; }
           summ "$O/ab_s${j}_$i.log" "[${SETS[$j]}]" | tee -a "$O/ab.txt"
