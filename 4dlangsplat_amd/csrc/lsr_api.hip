@@ -183,15 +183,21 @@ struct Img {
     uint32_t* n_contrib;
     uint32_t* tile_order;   // backward scratch: tiles by descending replay length
 };
+// the tile grid of a W x H image
+struct Grid { int x, y; size_t tiles() const { return (size_t)x * y; } };
+Grid tile_grid(int W, int H) { return {(W + LSR_TILE_X - 1) / LSR_TILE_X, (H + LSR_TILE_Y - 1) / LSR_TILE_Y}; }
+// focal length in pixels of an image axis
+float focal(int extent, float tanfov) { return (float)extent / (2.0f * tanfov); }
+
 Img carve_img(void* base, int W, int H, size_t* bytes) {
-    const size_t gx = (W + LSR_TILE_X - 1) / LSR_TILE_X, gy = (H + LSR_TILE_Y - 1) / LSR_TILE_Y;
+    const size_t ntiles = tile_grid(W, H).tiles();
     Carver c(base);
     Img m;
-    m.ranges = c.take<uint2>(gx * gy);
-    m.tile_max = c.take<uint32_t>(gx * gy);
+    m.ranges = c.take<uint2>(ntiles);
+    m.tile_max = c.take<uint32_t>(ntiles);
     m.final_T = c.take<float>((size_t)W * H);
     m.n_contrib = c.take<uint32_t>((size_t)W * H);
-    m.tile_order = c.take<uint32_t>(gx * gy);
+    m.tile_order = c.take<uint32_t>(ntiles);
     if (bytes) *bytes = c.off;
     return m;
 }
@@ -222,6 +228,8 @@ int tile_bits(int ntiles) {
     return b;
 }
 bool tile_sort_in_b(int ntiles) { return ((tile_bits(ntiles) + 7) / 8) % 2 == 1; }
+// the binning's sorted point list: where the compositors read
+uint32_t* point_list(const Binning& b, Grid grid) { return tile_sort_in_b((int)grid.tiles()) ? b.val_b : b.val_a; }
 int depth_sort_result_in_b() { return 0; }  // 4 passes, or 3 planned on the device: either way in the (a) buffers
 
 int check_common(const lsr_settings* s, const lsr_fwd_in* in) {
@@ -255,11 +263,68 @@ int check_common(const lsr_settings* s, const lsr_fwd_in* in) {
     return LSR_OK;
 }
 
+// ---- validation of a batch of views -------------------------------------------------------------
+// What a batched entry point says when n_views < 1 and when a per-view array is null, and the
+// settings its views must share with view 0 (share_first: compared before the entry point's own
+// per-view requirements, the binnings' order; otherwise after them).
+enum : unsigned { SHARE_SIZE = 1, SHARE_SH_DEGREE = 2, SHARE_SCALE = 4, SHARE_FEATURE = 8 };
+struct ViewRules { const char *no_views, *null_array; unsigned share; const char* share_msg; bool share_first; };
+const char kArrays[] = "n_views >= 1 and the per-view arrays are required";
+const ViewRules kPreprocessViews{kArrays, kArrays, SHARE_SIZE | SHARE_SH_DEGREE | SHARE_SCALE,
+                                 "batched views must share the image size, sh_degree and scale_modifier", false};
+const ViewRules kBinningViews{kArrays, kArrays, SHARE_SIZE, "batched views must share the image size", true};
+const ViewRules kCompositeViews{kArrays, kArrays, SHARE_SIZE | SHARE_FEATURE,
+                                "batched views must share the image size and include_feature", false};
+const ViewRules kBackwardViews{"n_views must be >= 1", "null argument", SHARE_SCALE,
+                               "all views must share scale_modifier", false};
+
+bool shares(const lsr_settings* a, const lsr_settings* b, unsigned what) {
+    return (!(what & SHARE_SIZE) || (a->image_width == b->image_width && a->image_height == b->image_height)) &&
+           (!(what & SHARE_SH_DEGREE) || a->sh_degree == b->sh_degree) &&
+           (!(what & SHARE_SCALE) || a->scale_modifier == b->scale_modifier) &&
+           (!(what & SHARE_FEATURE) || (a->include_feature != 0) == (b->include_feature != 0));
+}
+
+// Every view is validated before anything is launched: n_views and the per-view arrays (arrays:
+// all non-null), then for each view check_common, the rules' shared settings and what the entry
+// point itself requires of the view (need(v): LSR_OK or a fail()).
+template <typename Need>
+int check_each_view(const ViewRules& rules, int32_t n_views, bool arrays, const lsr_settings* const* s,
+                    const lsr_fwd_in* in, Need need) {
+    if (n_views < 1) return fail(LSR_EINVAL, rules.no_views);
+    if (!arrays) return fail(LSR_EINVAL, rules.null_array);
+    for (int v = 0; v < n_views; ++v) {
+        int rc = check_common(s[v], in);
+        if (rc) return rc;
+        if (rules.share_first && !shares(s[v], s[0], rules.share)) return fail(LSR_EINVAL, rules.share_msg);
+        if ((rc = need(v))) return rc;
+        if (!rules.share_first && !shares(s[v], s[0], rules.share)) return fail(LSR_EINVAL, rules.share_msg);
+    }
+    return LSR_OK;
+}
+int need_radii(int32_t n_views, lsr_fwd_out* const* out, int P) {
+    for (int v = 0; v < n_views; ++v)
+        if (!out[v] || (!out[v]->radii && P > 0)) return fail(LSR_EINVAL, "radii output is required");
+    return LSR_OK;
+}
+// a rendered view's workspaces (no binning workspace when nothing was listed)
+int need_workspaces(const void* geom, const void* img, const void* binning, int64_t num_rendered) {
+    if (!geom || !img || (num_rendered > 0 && !binning)) return fail(LSR_EINVAL, "workspaces are required");
+    return LSR_OK;
+}
+// a view's upstream gradients, for the float-atomic reductions
+int need_atomic_grads(const lsr_bwd_in* gin, const char* color_msg, const char* deterministic_msg) {
+    if (!gin || !gin->dL_dout_color) return fail(LSR_EINVAL, color_msg);
+    if (gin->deterministic) return fail(LSR_EINVAL, deterministic_msg);
+    return LSR_OK;
+}
+
 // The Gaussians' side of a preprocess launch (shared by its views).
 void preprocess_shared(lsr::PreprocessArgs& a, const lsr_settings* s, const lsr_fwd_in* in) {
     const int W = s->image_width, H = s->image_height;
+    const Grid grid = tile_grid(W, H);
     a.P = in->P; a.M = in->M; a.deg = s->sh_degree; a.W = W; a.H = H;
-    a.grid_x = (W + LSR_TILE_X - 1) / LSR_TILE_X; a.grid_y = (H + LSR_TILE_Y - 1) / LSR_TILE_Y;
+    a.grid_x = grid.x; a.grid_y = grid.y;
     a.scale_modifier = s->scale_modifier;
     a.means3D = in->means3D; a.scales = in->scales; a.rotations = in->rotations; a.opacities = in->opacities;
     a.shs = in->shs; a.colors_precomp = in->colors_precomp; a.cov3D_precomp = in->cov3D_precomp;
@@ -269,8 +334,8 @@ void preprocess_shared(lsr::PreprocessArgs& a, const lsr_settings* s, const lsr_
 // [0] K, [1..2] reserved (reported as 0), [3] visible count: no separate fill launches.
 void preprocess_view(lsr::PreprocessView& v, const lsr_settings* s, const Geom& g, int* radii) {
     v.tanfovx = s->tanfovx; v.tanfovy = s->tanfovy;
-    v.focal_x = (float)s->image_width / (2.0f * s->tanfovx);
-    v.focal_y = (float)s->image_height / (2.0f * s->tanfovy);
+    v.focal_x = focal(s->image_width, s->tanfovx);
+    v.focal_y = focal(s->image_height, s->tanfovy);
     v.view = s->viewmatrix; v.proj = s->projmatrix; v.campos = s->campos;
     v.radii = radii; v.radius = g.radius; v.tiles = g.tiles; v.rect = g.rect; v.key = g.key_a; v.xy = g.xy;
     v.conic_o = g.conic_o; v.rgbd = g.rgbd; v.clamped = g.clamped;
@@ -279,6 +344,229 @@ void preprocess_view(lsr::PreprocessView& v, const lsr_settings* s, const Geom& 
     v.acc = g.acc;
     v.clear.p[0] = g.total;
     v.clear.n[0] = 4;
+}
+
+// The device alias of page-locked host_counts (the instance scan then writes the counts itself), or
+// null: pageable memory, the counts are copied.
+uint32_t* mapped_counts(uint32_t* host_counts) {
+    void* dptr = nullptr;
+    if (hipHostGetDevicePointer(&dptr, host_counts, 0) == hipSuccess && dptr) return static_cast<uint32_t*>(dptr);
+    (void)hipGetLastError();   // clear the sticky error of the failed query
+    return nullptr;
+}
+
+// Instance scan of nv <= 8 views (their geom workspaces: the exclusive scan of g.counts into
+// g.offsets, the total K into g.total[0]) and the delivery of each view's [K, reserved = 0] to
+// host_counts: with `mapped`, host_counts' device alias, the scan writes K straight to the caller's
+// pinned word (the preprocess zeroed a view's reserved word only on the device: the host clears it
+// here); the views it did not write (one-tile scans; mapped == null) get a copy of g.total[0..1].
+int scan_counts(int nv, void* const* geom, int P, uint32_t* host_counts, uint32_t* mapped, hipStream_t st, bool debug) {
+    lsr::ScanSeg sc[lsr::LSR_MAX_VIEWS] = {};
+    const uint32_t* total[lsr::LSR_MAX_VIEWS];
+    for (int k = 0; k < nv; ++k) {
+        Geom g = carve_geom(geom[k], (size_t)P, nullptr);
+        sc[k] = lsr::ScanSeg{g.counts, g.offsets, g.total, reinterpret_cast<uint32_t*>(g.scan_tmp), (size_t)P};
+        total[k] = g.total;
+        if (mapped) {
+            sc[k].host_total = mapped + 2 * k;
+            host_counts[2 * k + 1] = 0;
+        }
+    }
+    uint32_t wrote;
+    {
+        PhaseTimer t(LSR_PHASE_INSTANCE_SCAN, st);
+        wrote = lsr::exclusive_scan_batch(sc, nv, st);
+    }
+    LSR_LAUNCHED("instance scan", st, debug);
+    for (int k = 0; k < nv; ++k)
+        if (!((wrote >> k) & 1u))
+            LSR_HIP(hipMemcpyAsync(host_counts + 2 * k, total[k], 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    return LSR_OK;
+}
+
+// ---- binning: the two algorithms' shared host path ----------------------------------------------
+// the batch (view 0's image) and a view with instances to list: its carved geom and img workspaces,
+// K and its binning workspace
+struct BinBatch { int P, W, H; Grid grid; size_t ntiles; hipStream_t st; bool debug; };
+struct BinView { Geom g; Img m; size_t K; void* binning; };
+// Validation (max_tiles: the algorithm's limit, refused with too_many_tiles), then per 8 views: a view
+// with K == 0 gets empty tile ranges and replay bounds, the others are handed to launch(batch, views,
+// count), one call for the set, which enqueues the algorithm's kernels.
+template <typename Launch>
+int bin_views(int32_t n_views, const lsr_settings* const* s, const lsr_fwd_in* in, void* const* geom,
+              void* const* binning, void* const* img, const int64_t* num_rendered, lsr_stream_t stream,
+              size_t max_tiles, const char* too_many_tiles, Launch launch) {
+    int rc = check_each_view(kBinningViews, n_views, s && geom && binning && img && num_rendered, s, in, [&](int v) {
+        return need_workspaces(geom[v], img[v], binning[v], num_rendered[v]);
+    });
+    if (rc) return rc;
+    const Grid grid = tile_grid(s[0]->image_width, s[0]->image_height);
+    const BinBatch c{in->P, s[0]->image_width, s[0]->image_height, grid, grid.tiles(),
+                     reinterpret_cast<hipStream_t>(stream), s[0]->debug != 0};
+    if (c.ntiles > max_tiles) return fail(LSR_EINVAL, too_many_tiles);
+    for (int v0 = 0; v0 < n_views; v0 += lsr::LSR_MAX_VIEWS) {
+        const int nv = std::min(n_views - v0, lsr::LSR_MAX_VIEWS);
+        BinView bv[lsr::LSR_MAX_VIEWS];
+        int ne = 0;
+        for (int v = v0; v < v0 + nv; ++v) {
+            const size_t K = (size_t)num_rendered[v];
+            Geom g = carve_geom(geom[v], (size_t)(c.P > 0 ? c.P : 1), nullptr);
+            Img m = carve_img(img[v], c.W, c.H, nullptr);
+            if (K == 0) {
+                LSR_HIP(hipMemsetAsync(m.ranges, 0, sizeof(uint2) * c.ntiles, c.st));
+                LSR_HIP(hipMemsetAsync(m.tile_max, 0, sizeof(uint32_t) * c.ntiles, c.st));
+                continue;
+            }
+            bv[ne++] = BinView{g, m, K, binning[v]};
+        }
+        if (ne == 0) continue;
+        if ((rc = launch(c, bv, ne))) return rc;
+    }
+    return LSR_OK;
+}
+
+// What the compositor backward reads of one view: its forward's workspaces, the inputs and the
+// upstream gradients.  The caller adds the reduction (mode, records or accumulators, dL/dlanguage).
+void render_bwd_view(lsr::RenderBwdArgs& r, const lsr_settings* s, const lsr_fwd_in* in, const lsr_bwd_in* gin,
+                     const Geom& g, const Binning& b, const Img& m) {
+    const int W = s->image_width, H = s->image_height;
+    const Grid grid = tile_grid(W, H);
+    r.W = W; r.H = H; r.grid_x = grid.x; r.grid_y = grid.y; r.C = in->C; r.include_feature = s->include_feature;
+    r.ranges = m.ranges; r.point_list = point_list(b, grid);
+    r.xy = g.xy; r.conic_o = g.conic_o; r.rgbd = g.rgbd;
+    r.rect = g.rect; r.inst_off = g.inst_off;
+    r.lang = in->language_feature;
+    r.lang_split = in->C == 32 ? in->language_feature_split : nullptr;
+    r.bg = s->bg; r.final_T = m.final_T; r.n_contrib = m.n_contrib;
+    r.tile_max_contrib = m.tile_max; r.tile_order = m.tile_order;
+    r.dL_dcolor = gin->dL_dout_color; r.dL_dlang = gin->dL_dout_language_feature; r.dL_ddepth = gin->dL_dout_depth;
+}
+
+}  // namespace
+
+// ---- forward phase 1: one host path, for one view as for n ----------------------------------------
+// These four helpers stay in an unnamed namespace inside extern "C": the compiler exports such
+// names, and the library's exported symbol set does not change here.
+extern "C" {
+namespace {
+// the preprocess family: each view needs its geom workspace
+int check_views(int32_t n_views, const lsr_settings* const* s, const lsr_fwd_in* in, void* const* geom) {
+    return check_each_view(kPreprocessViews, n_views, s && geom, s, in,
+                           [&](int v) { return geom[v] ? LSR_OK : fail(LSR_EINVAL, "geom workspaces are required"); });
+}
+
+// preprocess of rows [row0, row1) of n_views validated views, one launch per 8 views; counts_tiles:
+// each view's counts array gets the per-Gaussian instance counts by id (the tile-bucket binning's
+// input) instead of zeros (the depth sort's last pass fills it by depth rank)
+int preprocess_rows(int32_t n_views, int32_t row0, int32_t row1, int counts_tiles, const lsr_settings* const* s,
+                    const lsr_fwd_in* in, lsr_fwd_out* const* out, void* const* geom, hipStream_t st) {
+    const int P = in->P;
+    if (row1 == row0) return LSR_OK;
+    for (int v0 = 0; v0 < n_views; v0 += lsr::LSR_MAX_VIEWS) {
+        const int nv = std::min(n_views - v0, lsr::LSR_MAX_VIEWS);
+        lsr::PreprocessArgs a{};
+        preprocess_shared(a, s[v0], in);
+        a.nv = nv;
+        a.row0 = row0;
+        a.P = row1;   // the launch's bound (every per-Gaussian array is indexed by the global row)
+        a.counts_tiles = counts_tiles;
+        for (int k = 0; k < nv; ++k) {
+            Geom g = carve_geom(geom[v0 + k], (size_t)P, nullptr);
+            preprocess_view(a.v[k], s[v0 + k], g, out[v0 + k]->radii);
+        }
+        {
+            PhaseTimer t(LSR_PHASE_PREPROCESS, st);
+            lsr::launch_preprocess(a, st);
+        }
+        LSR_LAUNCHED("preprocess", st, s[v0]->debug);
+    }
+    return LSR_OK;
+}
+
+// depth order + instance count of n_views preprocessed views, one set of launches per 8 views
+int depth_order_views(int32_t n_views, const lsr_settings* const* s, const lsr_fwd_in* in, void* const* geom,
+                      uint32_t* host_counts, uint32_t* mapped, hipStream_t st) {
+    const int P = in->P;
+    for (int v0 = 0; v0 < n_views; v0 += lsr::LSR_MAX_VIEWS) {
+        const int nv = std::min(n_views - v0, lsr::LSR_MAX_VIEWS);
+        lsr::SortSeg ss[lsr::LSR_MAX_VIEWS] = {};
+        for (int k = 0; k < nv; ++k) {
+            Geom g = carve_geom(geom[v0 + k], (size_t)P, nullptr);
+            // depth order of the visible Gaussians, stable in id (the first pass drops culled keys,
+            // 0xFFFFFFFF, kept count in g.total[3]; the last pass writes the depth-ranked rectangles
+            // and instance counts: the ranks of culled Gaussians keep the preprocess's zero counts)
+            ss[k] = lsr::SortSeg{g.key_a, g.val_a, g.key_b, g.val_b, g.sort_tmp, g.total + 3,
+                                 lsr::SortGather{g.rect, g.counts, g.rect_sorted}, (size_t)P};
+            ss[k].vals_c = g.offsets;   // the device-planned passes' scratch (free until the instance scan)
+        }
+        {
+            PhaseTimer t(LSR_PHASE_DEPTH_SORT, st);
+            if (lsr::radix_sort_batch(ss, nv, 0, 32, st) != depth_sort_result_in_b())
+                return fail(LSR_EHIP, "internal: depth sort batch or parity");
+        }
+        LSR_LAUNCHED("depth sort", st, s[v0]->debug);
+        int rc = scan_counts(nv, geom + v0, P, host_counts + 2 * v0, mapped ? mapped + 2 * v0 : nullptr, st,
+                             s[v0]->debug);
+        if (rc) return rc;
+    }
+    return LSR_OK;
+}
+
+// the tile-bucket binning's instance count: the exclusive scan of the per-Gaussian counts in id
+// order (no depth sort), one launch set per 8 views
+int instance_scan_views(int32_t n_views, const lsr_fwd_in* in, void* const* geom, uint32_t* host_counts,
+                        uint32_t* mapped, hipStream_t st, bool debug) {
+    for (int v0 = 0; v0 < n_views; v0 += lsr::LSR_MAX_VIEWS) {
+        int rc = scan_counts(std::min(n_views - v0, lsr::LSR_MAX_VIEWS), geom + v0, in->P, host_counts + 2 * v0,
+                             mapped ? mapped + 2 * v0 : nullptr, st, debug);
+        if (rc) return rc;
+    }
+    return LSR_OK;
+}
+}  // namespace
+}  // extern "C"
+
+namespace {
+// Phase 1 of n_views validated views: the preprocess of all rows, then the depth order and instance
+// count of the first n_ordered.  map_counts: host_counts is page-locked, its counts come through its
+// device alias; otherwise it may be pageable and they are copied.
+int preprocess_and_order(int32_t n_views, int32_t n_ordered, const lsr_settings* const* s, const lsr_fwd_in* in,
+                         lsr_fwd_out* const* out, void* const* geom, uint32_t* host_counts, bool map_counts,
+                         hipStream_t st) {
+    if (in->P == 0) {
+        for (int v = 0; v < 2 * n_ordered; ++v) host_counts[v] = 0;
+        return LSR_OK;
+    }
+    int rc = preprocess_rows(n_views, 0, in->P, 0, s, in, out, geom, st);
+    if (rc || n_ordered == 0) return rc;
+    return depth_order_views(n_ordered, s, in, geom, host_counts, map_counts ? mapped_counts(host_counts) : nullptr, st);
+}
+
+// lsr_forward_preprocess_views_rows_async and its tile-bucket twin
+int preprocess_rows_checked(int32_t n_views, int32_t row0, int32_t row1, int counts_tiles, const lsr_settings* const* s,
+                            const lsr_fwd_in* in, lsr_fwd_out* const* out, void* const* geom, lsr_stream_t stream) {
+    int rc = check_views(n_views, s, in, geom);
+    if (rc) return rc;
+    if (!out || row0 < 0 || row1 < row0 || row1 > in->P || row0 % 256 != 0)
+        return fail(LSR_EINVAL, "0 <= row0 <= row1 <= P with row0 a multiple of 256, and the outputs are required");
+    if ((rc = need_radii(n_views, out, in->P))) return rc;
+    return preprocess_rows(n_views, row0, row1, counts_tiles, s, in, out, geom, reinterpret_cast<hipStream_t>(stream));
+}
+
+// lsr_forward_depth_order_views_async (depth_sort) and lsr_forward_instance_scan_views_async
+int count_views(int32_t n_views, const lsr_settings* const* s, const lsr_fwd_in* in, void* const* geom,
+                uint32_t* host_counts, lsr_stream_t stream, bool depth_sort) {
+    int rc = check_views(n_views, s, in, geom);
+    if (rc) return rc;
+    if (!host_counts) return fail(LSR_EINVAL, "host_counts is required");
+    if (in->P == 0) {
+        for (int v = 0; v < 2 * n_views; ++v) host_counts[v] = 0;
+        return LSR_OK;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    uint32_t* mapped = mapped_counts(host_counts);
+    return depth_sort ? depth_order_views(n_views, s, in, geom, host_counts, mapped, st)
+                      : instance_scan_views(n_views, in, geom, host_counts, mapped, st, s[0]->debug);
 }
 
 }  // namespace
@@ -307,9 +595,8 @@ int64_t lsr_binning_bytes(int64_t K) {
 }
 int64_t lsr_binning_bytes_tb(int64_t K, int32_t P, int32_t W, int32_t H) {
     if (W <= 0 || H <= 0 || P < 0) return -1;
-    const size_t ntiles = (size_t)((W + LSR_TILE_X - 1) / LSR_TILE_X) * ((H + LSR_TILE_Y - 1) / LSR_TILE_Y);
     size_t b;
-    carve_binning_tb(nullptr, (size_t)(K > 0 ? K : 1), (size_t)(P > 0 ? P : 1), ntiles, &b);
+    carve_binning_tb(nullptr, (size_t)(K > 0 ? K : 1), (size_t)(P > 0 ? P : 1), tile_grid(W, H).tiles(), &b);
     return (int64_t)b;
 }
 int64_t lsr_img_bytes(int32_t W, int32_t H) {
@@ -328,111 +615,11 @@ int lsr_forward_preprocess_async(const lsr_settings* s, const lsr_fwd_in* in, ls
                                  uint32_t* host_count, lsr_stream_t stream) {
     int rc = check_common(s, in);
     if (rc) return rc;
-    if (!out || (!out->radii && in->P > 0)) return fail(LSR_EINVAL, "radii output is required");
+    if ((rc = need_radii(1, &out, in->P))) return rc;
     if (!geom || !host_count) return fail(LSR_EINVAL, "geom workspace and host_count are required");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int P = in->P;
-    Geom g = carve_geom(geom, (size_t)(P > 0 ? P : 1), nullptr);
-    if (P == 0) {
-        host_count[0] = host_count[1] = 0;
-        return LSR_OK;
-    }
-    lsr::PreprocessArgs a{};
-    preprocess_shared(a, s, in);
-    a.nv = 1;
-    preprocess_view(a.v[0], s, g, out->radii);
-    {
-        PhaseTimer t(LSR_PHASE_PREPROCESS, st);
-        lsr::launch_preprocess(a, st);
-    }
-    LSR_LAUNCHED("preprocess", st, s->debug);
-    // depth order of all Gaussians (culled ones carry key 0xFFFFFFFF and sort last), stable in id
-    bool in_b;
-    {
-        PhaseTimer t(LSR_PHASE_DEPTH_SORT, st);
-        // culled Gaussians (key 0xFFFFFFFF) are dropped by the first pass: the visible count goes
-        // to g.total[3] and only those are sorted (and gathered below)
-        // ... and its last pass writes the depth-ranked rectangles and instance counts (the ranks
-        // of culled Gaussians keep the zero counts the preprocess wrote)
-        const lsr::SortGather gather{g.rect, g.counts, g.rect_sorted};
-        in_b = lsr::radix_sort_pairs(g.key_a, g.val_a, g.key_b, g.val_b, (size_t)P, 0, 32, g.sort_tmp, st, g.total + 3,
-                                     &gather, g.offsets);   // offsets: free until the instance scan
-    }
-    if (in_b != (bool)depth_sort_result_in_b()) return fail(LSR_EHIP, "internal: depth sort parity");
-    LSR_LAUNCHED("depth sort", st, s->debug);
-    {
-        PhaseTimer t(LSR_PHASE_INSTANCE_SCAN, st);
-        lsr::exclusive_scan_u32(g.counts, g.offsets, (size_t)P, g.total, g.scan_tmp, st);
-    }
-    LSR_LAUNCHED("instance scan", st, s->debug);
-    LSR_HIP(hipMemcpyAsync(host_count, g.total, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    return LSR_OK;
+    // the one-view batch; host_count may be pageable (lsr_forward_preprocess's is): always copied
+    return preprocess_and_order(1, 1, &s, in, &out, &geom, host_count, false, reinterpret_cast<hipStream_t>(stream));
 }
-
-namespace {
-int check_views(int32_t n_views, const lsr_settings* const* s, const lsr_fwd_in* in, void* const* geom) {
-    if (n_views < 1 || !s || !geom) return fail(LSR_EINVAL, "n_views >= 1 and the per-view arrays are required");
-    for (int v = 0; v < n_views; ++v) {
-        int rc = check_common(s[v], in);
-        if (rc) return rc;
-        if (!geom[v]) return fail(LSR_EINVAL, "geom workspaces are required");
-        if (s[v]->image_width != s[0]->image_width || s[v]->image_height != s[0]->image_height ||
-            s[v]->sh_degree != s[0]->sh_degree || s[v]->scale_modifier != s[0]->scale_modifier)
-            return fail(LSR_EINVAL, "batched views must share the image size, sh_degree and scale_modifier");
-    }
-    return LSR_OK;
-}
-
-// depth order + instance count of n_views preprocessed views (their geom workspaces), one set of
-// launches per 8 views; page-locked host_counts get the counts from the scan itself
-int depth_order_views(int32_t n_views, const lsr_settings* const* s, const lsr_fwd_in* in, void* const* geom,
-                      uint32_t* host_counts, hipStream_t st) {
-    const int P = in->P;
-    uint32_t* mapped = nullptr;
-    {
-        void* dptr = nullptr;
-        if (hipHostGetDevicePointer(&dptr, host_counts, 0) == hipSuccess && dptr) mapped = static_cast<uint32_t*>(dptr);
-        else (void)hipGetLastError();   // clear the sticky error of the failed query
-    }
-    for (int v0 = 0; v0 < n_views; v0 += lsr::LSR_MAX_VIEWS) {
-        const int nv = std::min(n_views - v0, lsr::LSR_MAX_VIEWS);
-        lsr::SortSeg ss[lsr::LSR_MAX_VIEWS] = {};
-        lsr::ScanSeg sc[lsr::LSR_MAX_VIEWS] = {};
-        for (int k = 0; k < nv; ++k) {
-            Geom g = carve_geom(geom[v0 + k], (size_t)P, nullptr);
-            // depth order of the visible Gaussians (the first pass drops culled keys, kept count in
-            // g.total[3]; the last pass writes the depth-ranked rectangles and instance counts)
-            ss[k] = lsr::SortSeg{g.key_a, g.val_a, g.key_b, g.val_b, g.sort_tmp, g.total + 3,
-                                 lsr::SortGather{g.rect, g.counts, g.rect_sorted}, (size_t)P};
-            ss[k].vals_c = g.offsets;   // the device-planned passes' scratch (free until the instance scan)
-            sc[k] = lsr::ScanSeg{g.counts, g.offsets, g.total, reinterpret_cast<uint32_t*>(g.scan_tmp), (size_t)P};
-            if (mapped) {   // the scan writes K straight to the caller's pinned word (the preprocess
-                sc[k].host_total = mapped + 2 * (v0 + k);   // zeroed a view's reserved word only on the
-                host_counts[2 * (v0 + k) + 1] = 0;           // device: the host clears it here)
-            }
-        }
-        {
-            PhaseTimer t(LSR_PHASE_DEPTH_SORT, st);
-            if (lsr::radix_sort_batch(ss, nv, 0, 32, st) != depth_sort_result_in_b())
-                return fail(LSR_EHIP, "internal: depth sort batch or parity");
-        }
-        LSR_LAUNCHED("depth sort", st, s[v0]->debug);
-        uint32_t wrote;
-        {
-            PhaseTimer t(LSR_PHASE_INSTANCE_SCAN, st);
-            wrote = lsr::exclusive_scan_batch(sc, nv, st);
-        }
-        LSR_LAUNCHED("instance scan", st, s[v0]->debug);
-        for (int k = 0; k < nv; ++k) {
-            if ((wrote >> k) & 1u) continue;
-            Geom g = carve_geom(geom[v0 + k], (size_t)P, nullptr);
-            LSR_HIP(hipMemcpyAsync(host_counts + 2 * (v0 + k), g.total, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                   st));
-        }
-    }
-    return LSR_OK;
-}
-}  // namespace
 
 int lsr_forward_preprocess_views_split_async(int32_t n_views, int32_t n_ordered, const lsr_settings* const* s,
                                              const lsr_fwd_in* in, lsr_fwd_out* const* out, void* const* geom,
@@ -441,140 +628,31 @@ int lsr_forward_preprocess_views_split_async(int32_t n_views, int32_t n_ordered,
     if (rc) return rc;
     if (!out || (n_ordered > 0 && !host_counts) || n_ordered < 0 || n_ordered > n_views)
         return fail(LSR_EINVAL, "0 <= n_ordered <= n_views, the outputs and host_counts are required");
-    for (int v = 0; v < n_views; ++v)
-        if (!out[v] || (!out[v]->radii && in->P > 0)) return fail(LSR_EINVAL, "radii output is required");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int P = in->P;
-    if (P == 0) {
-        for (int v = 0; v < 2 * n_ordered; ++v) host_counts[v] = 0;
-        return LSR_OK;
-    }
-    for (int v0 = 0; v0 < n_views; v0 += lsr::LSR_MAX_VIEWS) {
-        const int nv = std::min(n_views - v0, lsr::LSR_MAX_VIEWS);
-        lsr::PreprocessArgs a{};
-        preprocess_shared(a, s[v0], in);
-        a.nv = nv;
-        for (int k = 0; k < nv; ++k) {
-            Geom g = carve_geom(geom[v0 + k], (size_t)P, nullptr);
-            preprocess_view(a.v[k], s[v0 + k], g, out[v0 + k]->radii);
-        }
-        {
-            PhaseTimer t(LSR_PHASE_PREPROCESS, st);
-            lsr::launch_preprocess(a, st);
-        }
-        LSR_LAUNCHED("preprocess", st, s[v0]->debug);
-    }
-    return n_ordered > 0 ? depth_order_views(n_ordered, s, in, geom, host_counts, st) : LSR_OK;
+    if ((rc = need_radii(n_views, out, in->P))) return rc;
+    return preprocess_and_order(n_views, n_ordered, s, in, out, geom, host_counts, true,
+                                reinterpret_cast<hipStream_t>(stream));
 }
-
-namespace {
-// preprocess of rows [row0, row1) of n_views views, one launch per 8 views; counts_tiles: each
-// view's counts array gets the per-Gaussian instance counts by id (the tile-bucket binning's input)
-// instead of zeros (the depth sort's last pass fills it by depth rank)
-int preprocess_rows(int32_t n_views, int32_t row0, int32_t row1, int counts_tiles, const lsr_settings* const* s,
-                    const lsr_fwd_in* in, lsr_fwd_out* const* out, void* const* geom, hipStream_t st) {
-    int rc = check_views(n_views, s, in, geom);
-    if (rc) return rc;
-    if (!out || row0 < 0 || row1 < row0 || row1 > in->P || row0 % 256 != 0)
-        return fail(LSR_EINVAL, "0 <= row0 <= row1 <= P with row0 a multiple of 256, and the outputs are required");
-    for (int v = 0; v < n_views; ++v)
-        if (!out[v] || (!out[v]->radii && in->P > 0)) return fail(LSR_EINVAL, "radii output is required");
-    const int P = in->P;
-    if (row1 == row0) return LSR_OK;
-    for (int v0 = 0; v0 < n_views; v0 += lsr::LSR_MAX_VIEWS) {
-        const int nv = std::min(n_views - v0, lsr::LSR_MAX_VIEWS);
-        lsr::PreprocessArgs a{};
-        preprocess_shared(a, s[v0], in);
-        a.nv = nv;
-        a.row0 = row0;
-        a.P = row1;   // the launch's bound (every per-Gaussian array is indexed by the global row)
-        a.counts_tiles = counts_tiles;
-        for (int k = 0; k < nv; ++k) {
-            Geom g = carve_geom(geom[v0 + k], (size_t)P, nullptr);
-            preprocess_view(a.v[k], s[v0 + k], g, out[v0 + k]->radii);
-        }
-        {
-            PhaseTimer t(LSR_PHASE_PREPROCESS, st);
-            lsr::launch_preprocess(a, st);
-        }
-        LSR_LAUNCHED("preprocess", st, s[v0]->debug);
-    }
-    return LSR_OK;
-}
-
-// the tile-bucket binning's instance count: the exclusive scan of the per-Gaussian counts in id
-// order (no depth sort), one launch set per 8 views; K to the page-locked host_counts as above
-int instance_scan_views(int32_t n_views, const lsr_fwd_in* in, void* const* geom, uint32_t* host_counts,
-                        hipStream_t st, bool debug) {
-    const int P = in->P;
-    uint32_t* mapped = nullptr;
-    {
-        void* dptr = nullptr;
-        if (hipHostGetDevicePointer(&dptr, host_counts, 0) == hipSuccess && dptr) mapped = static_cast<uint32_t*>(dptr);
-        else (void)hipGetLastError();
-    }
-    for (int v0 = 0; v0 < n_views; v0 += lsr::LSR_MAX_VIEWS) {
-        const int nv = std::min(n_views - v0, lsr::LSR_MAX_VIEWS);
-        lsr::ScanSeg sc[lsr::LSR_MAX_VIEWS] = {};
-        for (int k = 0; k < nv; ++k) {
-            Geom g = carve_geom(geom[v0 + k], (size_t)P, nullptr);
-            sc[k] = lsr::ScanSeg{g.counts, g.offsets, g.total, reinterpret_cast<uint32_t*>(g.scan_tmp), (size_t)P};
-            if (mapped) {
-                sc[k].host_total = mapped + 2 * (v0 + k);
-                host_counts[2 * (v0 + k) + 1] = 0;
-            }
-        }
-        uint32_t wrote;
-        {
-            PhaseTimer t(LSR_PHASE_INSTANCE_SCAN, st);
-            wrote = lsr::exclusive_scan_batch(sc, nv, st);
-        }
-        LSR_LAUNCHED("instance scan", st, debug);
-        for (int k = 0; k < nv; ++k) {
-            if ((wrote >> k) & 1u) continue;
-            Geom g = carve_geom(geom[v0 + k], (size_t)P, nullptr);
-            LSR_HIP(hipMemcpyAsync(host_counts + 2 * (v0 + k), g.total, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                   st));
-        }
-    }
-    return LSR_OK;
-}
-}  // namespace
 
 int lsr_forward_preprocess_views_rows_async(int32_t n_views, int32_t row0, int32_t row1, const lsr_settings* const* s,
                                             const lsr_fwd_in* in, lsr_fwd_out* const* out, void* const* geom,
                                             lsr_stream_t stream) {
-    return preprocess_rows(n_views, row0, row1, 0, s, in, out, geom, reinterpret_cast<hipStream_t>(stream));
+    return preprocess_rows_checked(n_views, row0, row1, 0, s, in, out, geom, stream);
 }
 
 int lsr_forward_preprocess_views_tb_async(int32_t n_views, int32_t row0, int32_t row1, const lsr_settings* const* s,
                                           const lsr_fwd_in* in, lsr_fwd_out* const* out, void* const* geom,
                                           lsr_stream_t stream) {
-    return preprocess_rows(n_views, row0, row1, 1, s, in, out, geom, reinterpret_cast<hipStream_t>(stream));
+    return preprocess_rows_checked(n_views, row0, row1, 1, s, in, out, geom, stream);
 }
 
 int lsr_forward_instance_scan_views_async(int32_t n_views, const lsr_settings* const* s, const lsr_fwd_in* in,
                                           void* const* geom, uint32_t* host_counts, lsr_stream_t stream) {
-    int rc = check_views(n_views, s, in, geom);
-    if (rc) return rc;
-    if (!host_counts) return fail(LSR_EINVAL, "host_counts is required");
-    if (in->P == 0) {
-        for (int v = 0; v < 2 * n_views; ++v) host_counts[v] = 0;
-        return LSR_OK;
-    }
-    return instance_scan_views(n_views, in, geom, host_counts, reinterpret_cast<hipStream_t>(stream), s[0]->debug);
+    return count_views(n_views, s, in, geom, host_counts, stream, false);
 }
 
 int lsr_forward_depth_order_views_async(int32_t n_views, const lsr_settings* const* s, const lsr_fwd_in* in,
                                         void* const* geom, uint32_t* host_counts, lsr_stream_t stream) {
-    int rc = check_views(n_views, s, in, geom);
-    if (rc) return rc;
-    if (!host_counts) return fail(LSR_EINVAL, "host_counts is required");
-    if (in->P == 0) {
-        for (int v = 0; v < 2 * n_views; ++v) host_counts[v] = 0;
-        return LSR_OK;
-    }
-    return depth_order_views(n_views, s, in, geom, host_counts, reinterpret_cast<hipStream_t>(stream));
+    return count_views(n_views, s, in, geom, host_counts, stream, true);
 }
 
 int lsr_forward_preprocess_views_async(int32_t n_views, const lsr_settings* const* s, const lsr_fwd_in* in,
@@ -603,41 +681,20 @@ int lsr_forward_binning(const lsr_settings* s, const lsr_fwd_in* in, void* geom,
 int lsr_forward_binning_views(int32_t n_views, const lsr_settings* const* s, const lsr_fwd_in* in, void* const* geom,
                               void* const* binning, void* const* img, const int64_t* num_rendered,
                               lsr_stream_t stream) {
-    if (n_views < 1 || !s || !geom || !binning || !img || !num_rendered)
-        return fail(LSR_EINVAL, "n_views >= 1 and the per-view arrays are required");
-    for (int v = 0; v < n_views; ++v) {
-        int rc = check_common(s[v], in);
-        if (rc) return rc;
-        if (s[v]->image_width != s[0]->image_width || s[v]->image_height != s[0]->image_height)
-            return fail(LSR_EINVAL, "batched views must share the image size");
-        if (!geom[v] || !img[v] || (num_rendered[v] > 0 && !binning[v])) return fail(LSR_EINVAL, "workspaces are required");
-    }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int P = in->P, W = s[0]->image_width, H = s[0]->image_height;
-    const int gx = (W + LSR_TILE_X - 1) / LSR_TILE_X, gy = (H + LSR_TILE_Y - 1) / LSR_TILE_Y;
-    const size_t ntiles = (size_t)gx * gy;
-    const int tbits = tile_bits((int)ntiles);
-    for (int v0 = 0; v0 < n_views; v0 += lsr::LSR_MAX_VIEWS) {
-        const int nv = std::min(n_views - v0, lsr::LSR_MAX_VIEWS);
+    const auto emit_and_sort = [](const BinBatch& c, const BinView* bv, int ne) {
+        const size_t ntiles = c.ntiles;
+        hipStream_t st = c.st;
         lsr::EmitBatch eb{};
-        eb.P = P; eb.grid_x = gx; eb.grid_y = gy; eb.W = W; eb.H = H;
+        eb.P = c.P; eb.grid_x = c.grid.x; eb.grid_y = c.grid.y; eb.W = c.W; eb.H = c.H;
         lsr::SortSeg ss[lsr::LSR_MAX_VIEWS] = {};
-        int ne = 0;
-        for (int k = 0; k < nv; ++k) {
-            const int v = v0 + k;
-            const size_t K = (size_t)num_rendered[v];
-            Geom g = carve_geom(geom[v], (size_t)(P > 0 ? P : 1), nullptr);
-            Img m = carve_img(img[v], W, H, nullptr);
-            if (K == 0) {
-                LSR_HIP(hipMemsetAsync(m.ranges, 0, sizeof(uint2) * ntiles, st));
-                LSR_HIP(hipMemsetAsync(m.tile_max, 0, sizeof(uint32_t) * ntiles, st));
-                continue;
-            }
-            Binning b = carve_binning(binning[v], K, nullptr);
+        for (int k = 0; k < ne; ++k) {
+            const Geom& g = bv[k].g;
+            const Img& m = bv[k].m;
+            Binning b = carve_binning(bv[k].binning, bv[k].K, nullptr);
             // the emission also presets the tile ranges (0xFFFFFFFF, 0) for the tile sort's last pass,
             // which makes them, and clears the per-tile replay bounds (no separate fill launches); the
             // forward compositor turns the ranges of empty tiles back into (0, 0)
-            lsr::EmitView& e = eb.v[ne];
+            lsr::EmitView& e = eb.v[k];
             e.order = g.val_a; e.offsets = g.offsets; e.counts = g.counts; e.rect_sorted = g.rect_sorted;
             e.xy = g.xy; e.conic_o = g.conic_o; e.keys = b.key_a; e.vals = b.val_a;
             e.clear.p[0] = reinterpret_cast<uint32_t*>(m.ranges);
@@ -647,62 +704,38 @@ int lsr_forward_binning_views(int32_t n_views, const lsr_settings* const* s, con
             e.clear.n[1] = (uint32_t)ntiles;
             // kept: the first pass drops the instances that reach no quadrant (key 0xFFFFFFFF, about
             // 10 % of them on the headline scene), the second sorts only the listed ones
-            ss[ne++] = lsr::SortSeg{b.key_a, b.val_a, b.key_b, b.val_b, b.sort_tmp, b.kept,
-                                    lsr::SortGather{nullptr, nullptr, nullptr}, K, m.ranges, (uint32_t)ntiles};
+            ss[k] = lsr::SortSeg{b.key_a, b.val_a, b.key_b, b.val_b, b.sort_tmp, b.kept,
+                                 lsr::SortGather{nullptr, nullptr, nullptr}, bv[k].K, m.ranges, (uint32_t)ntiles};
         }
-        if (ne == 0) continue;
         {
             PhaseTimer t(LSR_PHASE_EMIT, st);
             lsr::launch_emit_instances(eb, ne, st);
         }
-        LSR_LAUNCHED("emit", st, s[0]->debug);
+        LSR_LAUNCHED("emit", st, c.debug);
         {
             PhaseTimer t(LSR_PHASE_TILE_SORT, st);
-            const int in_b = lsr::radix_sort_batch(ss, ne, 0, tbits, st);   // one set of launches for all views
+            // one set of launches for all views
+            const int in_b = lsr::radix_sort_batch(ss, ne, 0, tile_bits((int)ntiles), st);
             if (in_b < 0 || (in_b == 1) != tile_sort_in_b((int)ntiles))
                 return fail(LSR_EHIP, "internal: tile sort batch or parity");
         }
-        LSR_LAUNCHED("tile sort", st, s[0]->debug);
-    }
-    return LSR_OK;
+        LSR_LAUNCHED("tile sort", st, c.debug);
+        return LSR_OK;
+    };
+    return bin_views(n_views, s, in, geom, binning, img, num_rendered, stream, SIZE_MAX, nullptr, emit_and_sort);
 }
 
 int lsr_forward_binning_views_tb(int32_t n_views, const lsr_settings* const* s, const lsr_fwd_in* in, void* const* geom,
                                  void* const* binning, void* const* img, const int64_t* num_rendered,
                                  lsr_stream_t stream) {
-    if (n_views < 1 || !s || !geom || !binning || !img || !num_rendered)
-        return fail(LSR_EINVAL, "n_views >= 1 and the per-view arrays are required");
-    for (int v = 0; v < n_views; ++v) {
-        int rc = check_common(s[v], in);
-        if (rc) return rc;
-        if (s[v]->image_width != s[0]->image_width || s[v]->image_height != s[0]->image_height)
-            return fail(LSR_EINVAL, "batched views must share the image size");
-        if (!geom[v] || !img[v] || (num_rendered[v] > 0 && !binning[v])) return fail(LSR_EINVAL, "workspaces are required");
-    }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int P = in->P, W = s[0]->image_width, H = s[0]->image_height;
-    const int gx = (W + LSR_TILE_X - 1) / LSR_TILE_X, gy = (H + LSR_TILE_Y - 1) / LSR_TILE_Y;
-    const size_t ntiles = (size_t)gx * gy;
-    // the per-block tile histograms live in LDS (4 bytes a tile)
-    if (ntiles > 12288)
-        return fail(LSR_EINVAL, "tile-bucket binning: more than 12288 tiles (use lsr_forward_binning_views)");
-    for (int v0 = 0; v0 < n_views; v0 += lsr::LSR_MAX_VIEWS) {
-        const int nv = std::min(n_views - v0, lsr::LSR_MAX_VIEWS);
+    const auto bucket = [](const BinBatch& c, const BinView* bv, int ne) {
         lsr::TbBatch tb{};
-        tb.P = P; tb.grid_x = gx; tb.grid_y = gy; tb.W = W; tb.H = H; tb.ntiles = (int)ntiles;
-        int ne = 0;
-        for (int k = 0; k < nv; ++k) {
-            const int v = v0 + k;
-            const size_t K = (size_t)num_rendered[v];
-            Geom g = carve_geom(geom[v], (size_t)(P > 0 ? P : 1), nullptr);
-            Img m = carve_img(img[v], W, H, nullptr);
-            if (K == 0) {
-                LSR_HIP(hipMemsetAsync(m.ranges, 0, sizeof(uint2) * ntiles, st));
-                LSR_HIP(hipMemsetAsync(m.tile_max, 0, sizeof(uint32_t) * ntiles, st));
-                continue;
-            }
-            BinningTb b = carve_binning_tb(binning[v], K, (size_t)P, ntiles, nullptr);
-            lsr::TbView& t = tb.v[ne++];
+        tb.P = c.P; tb.grid_x = c.grid.x; tb.grid_y = c.grid.y; tb.W = c.W; tb.H = c.H; tb.ntiles = (int)c.ntiles;
+        for (int k = 0; k < ne; ++k) {
+            const Geom& g = bv[k].g;
+            const Img& m = bv[k].m;
+            BinningTb b = carve_binning_tb(bv[k].binning, bv[k].K, (size_t)c.P, c.ntiles, nullptr);
+            lsr::TbView& t = tb.v[k];
             t.counts = g.counts; t.offsets = g.offsets; t.rect = g.rect; t.xy = g.xy; t.conic_o = g.conic_o;
             t.depth = g.key_a;
             t.table = b.table;
@@ -711,19 +744,21 @@ int lsr_forward_binning_views_tb(int32_t n_views, const lsr_settings* const* s, 
             t.ranges = m.ranges;
             t.keys = reinterpret_cast<uint64_t*>(b.b.key_a);
             t.tmp = b.tmp;
-            t.words = tile_sort_in_b((int)ntiles) ? b.b.val_b : b.b.val_a;   // where the compositors read
+            t.words = point_list(b.b, c.grid);
             t.tile_max = m.tile_max;
         }
-        if (ne == 0) continue;
         {
-            PhaseTimer t(LSR_PHASE_TILE_SORT, st);
-            const hipError_t e = lsr::launch_tile_bucket_binning(tb, ne, st);
+            PhaseTimer t(LSR_PHASE_TILE_SORT, c.st);
+            const hipError_t e = lsr::launch_tile_bucket_binning(tb, ne, c.st);
             if (e != hipSuccess)
                 return fail(LSR_EHIP, std::string("tile-bucket binning: dynamic LDS attribute: ") + hipGetErrorString(e));
         }
-        LSR_LAUNCHED("tile-bucket binning", st, s[0]->debug);
-    }
-    return LSR_OK;
+        LSR_LAUNCHED("tile-bucket binning", c.st, c.debug);
+        return LSR_OK;
+    };
+    // the per-block tile histograms live in LDS (4 bytes a tile)
+    return bin_views(n_views, s, in, geom, binning, img, num_rendered, stream, 12288,
+                     "tile-bucket binning: more than 12288 tiles (use lsr_forward_binning_views)", bucket);
 }
 
 int lsr_forward_composite(const lsr_settings* s, const lsr_fwd_in* in, lsr_fwd_out* out, const void* geom,
@@ -735,22 +770,16 @@ int lsr_forward_composite(const lsr_settings* s, const lsr_fwd_in* in, lsr_fwd_o
 int lsr_forward_composite_views(int32_t n_views, const lsr_settings* const* s, const lsr_fwd_in* in,
                                 lsr_fwd_out* const* out, const void* const* geom, const void* const* binning,
                                 void* const* img, const int64_t* num_rendered, lsr_stream_t stream) {
-    if (n_views < 1 || !s || !out || !geom || !binning || !img || !num_rendered)
-        return fail(LSR_EINVAL, "n_views >= 1 and the per-view arrays are required");
-    for (int v = 0; v < n_views; ++v) {   // every view validated before anything is launched
-        int rc = check_common(s[v], in);
-        if (rc) return rc;
+    int rc = check_each_view(kCompositeViews, n_views, s && out && geom && binning && img && num_rendered, s, in, [&](int v) {
         if (!out[v] || !out[v]->out_color || !out[v]->out_depth) return fail(LSR_EINVAL, "color and depth outputs are required");
         if (in->C > 0 && !out[v]->out_language_feature)
             return fail(LSR_EINVAL, "language feature output is required when C > 0");
-        if (!geom[v] || !img[v] || (num_rendered[v] > 0 && !binning[v])) return fail(LSR_EINVAL, "workspaces are required");
-        if (s[v]->image_width != s[0]->image_width || s[v]->image_height != s[0]->image_height ||
-            (s[v]->include_feature != 0) != (s[0]->include_feature != 0))
-            return fail(LSR_EINVAL, "batched views must share the image size and include_feature");
-    }
+        return need_workspaces(geom[v], img[v], binning[v], num_rendered[v]);
+    });
+    if (rc) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int P = in->P, W = s[0]->image_width, H = s[0]->image_height, C = in->C;
-    const int gx = (W + LSR_TILE_X - 1) / LSR_TILE_X, gy = (H + LSR_TILE_Y - 1) / LSR_TILE_Y;
+    const Grid grid = tile_grid(W, H);
     for (int v0 = 0; v0 < n_views; v0 += lsr::LSR_MAX_VIEWS) {
         const int nv = std::min(n_views - v0, lsr::LSR_MAX_VIEWS);
         lsr::RenderFwdArgs r[lsr::LSR_MAX_VIEWS] = {};
@@ -761,8 +790,8 @@ int lsr_forward_composite_views(int32_t n_views, const lsr_settings* const* s, c
             Binning b = carve_binning(const_cast<void*>(binning[v]), K > 0 ? K : 1, nullptr);
             Img m = carve_img(img[v], W, H, nullptr);   // tile_max was zeroed by the binning (atomicMax: idempotent)
             lsr::RenderFwdArgs& a = r[k];
-            a.W = W; a.H = H; a.grid_x = gx; a.grid_y = gy; a.C = C; a.include_feature = s[v]->include_feature;
-            a.ranges = m.ranges; a.point_list = K > 0 ? (tile_sort_in_b(gx * gy) ? b.val_b : b.val_a) : nullptr;
+            a.W = W; a.H = H; a.grid_x = grid.x; a.grid_y = grid.y; a.C = C; a.include_feature = s[v]->include_feature;
+            a.ranges = m.ranges; a.point_list = K > 0 ? point_list(b, grid) : nullptr;
             a.xy = g.xy; a.conic_o = g.conic_o; a.rgbd = g.rgbd;
             a.lang = in->language_feature;
             a.lang_split = in->C == 32 ? in->language_feature_split : nullptr;
@@ -810,7 +839,6 @@ int lsr_backward(const lsr_settings* s, const lsr_fwd_in* in, const lsr_bwd_in* 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int P = in->P, W = s->image_width, H = s->image_height, C = in->C;
     if (P == 0) return LSR_OK;
-    const int gx = (W + LSR_TILE_X - 1) / LSR_TILE_X, gy = (H + LSR_TILE_Y - 1) / LSR_TILE_Y;
     const size_t K = (size_t)num_rendered;
     Geom g = carve_geom(const_cast<void*>(geom), (size_t)P, nullptr);
     Binning b = carve_binning(const_cast<void*>(binning), K > 0 ? K : 1, nullptr);
@@ -829,16 +857,9 @@ int lsr_backward(const lsr_settings* s, const lsr_fwd_in* in, const lsr_bwd_in* 
     // when they are on)
     if (!accumulate && C > 0 && gout->dL_dlanguage_feature && (!det || Ceff == 0))
         LSR_HIP(hipMemsetAsync(gout->dL_dlanguage_feature, 0, sizeof(float) * (size_t)P * C, st));
-    const uint32_t* point_list = tile_sort_in_b(gx * gy) ? b.val_b : b.val_a;
     if (K > 0) {
         lsr::RenderBwdArgs r{};
-        r.W = W; r.H = H; r.grid_x = gx; r.grid_y = gy; r.C = C; r.include_feature = s->include_feature;
-        r.ranges = m.ranges; r.point_list = point_list; r.xy = g.xy; r.conic_o = g.conic_o; r.rgbd = g.rgbd;
-        r.rect = g.rect; r.inst_off = g.inst_off;
-        r.lang = in->language_feature;
-    r.lang_split = in->C == 32 ? in->language_feature_split : nullptr; r.bg = s->bg; r.final_T = m.final_T; r.n_contrib = m.n_contrib;
-        r.tile_max_contrib = m.tile_max; r.tile_order = m.tile_order;
-        r.dL_dcolor = gin->dL_dout_color; r.dL_dlang = gin->dL_dout_language_feature; r.dL_ddepth = gin->dL_dout_depth;
+        render_bwd_view(r, s, in, gin, g, b, m);
         r.rec = sc.rec; r.flags = sc.flags; r.recq = recq; r.deterministic = det;
         r.acc_small = sc.acc_small; r.acc_lang = gout->dL_dlanguage_feature;
         {
@@ -850,8 +871,8 @@ int lsr_backward(const lsr_settings* s, const lsr_fwd_in* in, const lsr_bwd_in* 
     lsr::PreprocessBwdArgs a{};
     a.P = P; a.M = in->M; a.deg = s->sh_degree;
     a.tanfovx = s->tanfovx; a.tanfovy = s->tanfovy;
-    a.focal_x = (float)W / (2.0f * s->tanfovx);
-    a.focal_y = (float)H / (2.0f * s->tanfovy);
+    a.focal_x = focal(W, s->tanfovx);
+    a.focal_y = focal(H, s->tanfovy);
     a.scale_modifier = s->scale_modifier;
     a.means3D = in->means3D; a.scales = in->scales; a.rotations = in->rotations; a.shs = in->shs;
     a.cov3D_precomp = in->cov3D_precomp; a.view = s->viewmatrix; a.proj = s->projmatrix; a.campos = s->campos;
@@ -884,24 +905,16 @@ int lsr_backward_composite_views(int32_t n_views, const lsr_settings* const* s, 
                                  const lsr_bwd_in* const* gin, float* dL_dlanguage, void* const* geom,
                                  const void* const* binning, const void* const* img, const int64_t* num_rendered,
                                  lsr_stream_t stream) {
-    if (n_views < 1 || !s || !gin || !geom || !binning || !img || !num_rendered)
-        return fail(LSR_EINVAL, "n_views >= 1 and the per-view arrays are required");
-    for (int v = 0; v < n_views; ++v) {   // every view validated before anything is launched
-        int rc = check_common(s[v], in);
-        if (rc) return rc;
-        if (!gin[v] || !gin[v]->dL_dout_color) return fail(LSR_EINVAL, "dL_dout_color is required");
-        if (gin[v]->deterministic)
-            return fail(LSR_EINVAL, "the split backward reduces with float atomics; use lsr_backward for deterministic "
-                                    "gradients");
-        if (!geom[v] || !img[v] || (num_rendered[v] > 0 && !binning[v])) return fail(LSR_EINVAL, "workspaces are required");
-        if (s[v]->image_width != s[0]->image_width || s[v]->image_height != s[0]->image_height ||
-            (s[v]->include_feature != 0) != (s[0]->include_feature != 0))
-            return fail(LSR_EINVAL, "batched views must share the image size and include_feature");
-    }
+    int rc = check_each_view(kCompositeViews, n_views, s && gin && geom && binning && img && num_rendered, s, in, [&](int v) {
+        int e = need_atomic_grads(gin[v], "dL_dout_color is required",
+                                  "the split backward reduces with float atomics; use lsr_backward for deterministic "
+                                  "gradients");
+        return e ? e : need_workspaces(geom[v], img[v], binning[v], num_rendered[v]);
+    });
+    if (rc) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int P = in->P, C = in->C, W = s[0]->image_width, H = s[0]->image_height;
     if (P == 0) return LSR_OK;
-    const int gx = (W + LSR_TILE_X - 1) / LSR_TILE_X, gy = (H + LSR_TILE_Y - 1) / LSR_TILE_Y;
     const int recq = lsr::record_floats(s[0]->include_feature ? C : 0);
     lsr::RenderBwdArgs r[lsr::LSR_MAX_VIEWS] = {};
     int nr = 0;
@@ -922,16 +935,7 @@ int lsr_backward_composite_views(int32_t n_views, const lsr_settings* const* s, 
         Binning b = carve_binning(const_cast<void*>(binning[v]), K, nullptr);
         Img m = carve_img(const_cast<void*>(img[v]), W, H, nullptr);
         lsr::RenderBwdArgs& a = r[nr++];
-        a.W = W; a.H = H; a.grid_x = gx; a.grid_y = gy; a.C = C; a.include_feature = s[v]->include_feature;
-        a.ranges = m.ranges; a.point_list = tile_sort_in_b(gx * gy) ? b.val_b : b.val_a;
-        a.xy = g.xy; a.conic_o = g.conic_o; a.rgbd = g.rgbd;
-        a.rect = g.rect; a.inst_off = g.inst_off;
-        a.lang = in->language_feature;
-        a.lang_split = in->C == 32 ? in->language_feature_split : nullptr;
-        a.bg = s[v]->bg; a.final_T = m.final_T; a.n_contrib = m.n_contrib;
-        a.tile_max_contrib = m.tile_max; a.tile_order = m.tile_order;
-        a.dL_dcolor = gin[v]->dL_dout_color; a.dL_dlang = gin[v]->dL_dout_language_feature;
-        a.dL_ddepth = gin[v]->dL_dout_depth;
+        render_bwd_view(a, s[v], in, gin[v], g, b, m);
         a.recq = recq; a.deterministic = 0;
         a.acc_small = reinterpret_cast<float*>(g.acc); a.acc_lang = dL_dlanguage;
         if (nr == lsr::LSR_MAX_VIEWS) launch();
@@ -951,14 +955,10 @@ int lsr_backward_preprocess_views(int32_t n_views, const lsr_settings* const* s,
 int lsr_backward_preprocess_views_rows(int32_t n_views, const lsr_settings* const* s, const lsr_fwd_in* in,
                                        lsr_bwd_out* gout, const void* const* geom, int32_t accumulate,
                                        int32_t row_begin, int32_t row_count, lsr_stream_t stream) {
-    if (n_views < 1) return fail(LSR_EINVAL, "n_views must be >= 1");
-    if (!s || !in || !gout || !geom) return fail(LSR_EINVAL, "null argument");
-    for (int v = 0; v < n_views; ++v) {
-        int rc = check_common(s[v], in);
-        if (rc) return rc;
-        if (!geom[v]) return fail(LSR_EINVAL, "the geom workspace is required for every view");
-        if (s[v]->scale_modifier != s[0]->scale_modifier) return fail(LSR_EINVAL, "all views must share scale_modifier");
-    }
+    int rc = check_each_view(kBackwardViews, n_views, s && in && gout && geom, s, in, [&](int v) {
+        return geom[v] ? LSR_OK : fail(LSR_EINVAL, "the geom workspace is required for every view");
+    });
+    if (rc) return rc;
     if (row_begin < 0 || row_count < 0 || (int64_t)row_begin + row_count > in->P)
         return fail(LSR_EINVAL, "rows [row_begin, row_begin + row_count) must lie inside [0, P)");
     if (row_begin % 256 != 0) return fail(LSR_EINVAL, "row_begin must be a multiple of 256");
@@ -985,8 +985,8 @@ int lsr_backward_preprocess_views_rows(int32_t n_views, const lsr_settings* cons
             lsr::ViewCam& c = a.cam[j];
             c.view = sv->viewmatrix; c.proj = sv->projmatrix; c.campos = sv->campos;
             c.tanfovx = sv->tanfovx; c.tanfovy = sv->tanfovy;
-            c.focal_x = (float)sv->image_width / (2.0f * sv->tanfovx);
-            c.focal_y = (float)sv->image_height / (2.0f * sv->tanfovy);
+            c.focal_x = focal(sv->image_width, sv->tanfovx);
+            c.focal_y = focal(sv->image_height, sv->tanfovy);
             c.deg = sv->sh_degree;
             c.tiles = g.tiles + r0; c.clamped = g.clamped + r0;
             c.acc_small = reinterpret_cast<const float*>(g.acc) + lsr::ACC_PITCH * r0;
@@ -1008,24 +1008,19 @@ int lsr_backward_views(int32_t n_views, const lsr_settings* const* s, const lsr_
                        const lsr_bwd_in* const* gin, lsr_bwd_out* gout, void* const* geom,
                        const void* const* binning, const void* const* img, const int64_t* num_rendered,
                        int32_t accumulate, lsr_stream_t stream) {
-    if (n_views < 1) return fail(LSR_EINVAL, "n_views must be >= 1");
-    if (!s || !in || !gin || !gout || !geom || !binning || !img || !num_rendered)
-        return fail(LSR_EINVAL, "null argument");
-    for (int v = 0; v < n_views; ++v) {   // validate every view before anything is launched
-        int rc = check_common(s[v], in);
-        if (rc) return rc;
-        if (!gin[v] || !gin[v]->dL_dout_color) return fail(LSR_EINVAL, "dL_dout_color is required for every view");
-        if (gin[v]->deterministic)
-            return fail(LSR_EINVAL, "lsr_backward_views reduces with float atomics; use lsr_backward per view for "
-                                    "deterministic gradients");
-        if (s[v]->scale_modifier != s[0]->scale_modifier) return fail(LSR_EINVAL, "all views must share scale_modifier");
-    }
+    int rc = check_each_view(kBackwardViews, n_views, s && in && gin && gout && geom && binning && img && num_rendered, s, in,
+                         [&](int v) {
+                             return need_atomic_grads(gin[v], "dL_dout_color is required for every view",
+                                                      "lsr_backward_views reduces with float atomics; use lsr_backward "
+                                                      "per view for deterministic gradients");
+                         });
+    if (rc) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int P = in->P, C = in->C;
     if (P == 0) return LSR_OK;
     if (!accumulate && C > 0 && gout->dL_dlanguage_feature)
         LSR_HIP(hipMemsetAsync(gout->dL_dlanguage_feature, 0, sizeof(float) * (size_t)P * C, st));
-    int rc = lsr_backward_composite_views(n_views, s, in, gin, gout->dL_dlanguage_feature, geom, binning, img,
+    rc = lsr_backward_composite_views(n_views, s, in, gin, gout->dL_dlanguage_feature, geom, binning, img,
                                           num_rendered, stream);
     if (rc) return rc;
     return lsr_backward_preprocess_views(n_views, s, in, gout, const_cast<const void* const*>(geom), accumulate,

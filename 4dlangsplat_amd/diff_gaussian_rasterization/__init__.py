@@ -69,6 +69,23 @@ def _f32(t, device):
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
+def _struct_array(cls, structs):
+    """cls* const* over ctypes structures (the per-view arrays of the *_views entry points)"""
+    return (ctypes.POINTER(cls) * len(structs))(*[ctypes.pointer(x) for x in structs])
+
+
+def _settings_array(settings):
+    return _struct_array(_lib.Settings, [s.c for s in settings])     # of _NativeSettings
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _int64_array(values):
+    return (ctypes.c_int64 * len(values))(*values)
+
+
 class _NativeSettings:
     """Keeps the device copies of the small settings tensors alive for the duration of a call."""
 
@@ -141,6 +158,15 @@ def _dump_forward(raster_settings, inputs):
         print("\nAn error occured in forward. Writing snapshot_fw.dump for debugging.")
 
 
+def _check_forward(rc, what, raster_settings, inputs):
+    """_lib.check of a forward entry point's return code; on failure the inputs are dumped (debug mode)."""
+    try:
+        _lib.check(rc, what)
+    except RuntimeError:
+        _dump_forward(raster_settings, inputs)
+        raise
+
+
 def _check_device(t):
     if t.device.type != "cuda":
         raise RuntimeError("the rasterizer runs on the GPU only (no CPU fallback); got tensors on " + str(t.device))
@@ -201,28 +227,21 @@ def preprocess_native(raster_settings, means3D, opacities, shs=None, colors_prec
     fout.radii = radii.data_ptr()
     if defer_count:
         count = torch.zeros(2, dtype=torch.int32, pin_memory=True)
-        try:
-            _lib.check(L.lsr_forward_preprocess_async(ctypes.byref(st.c), ctypes.byref(fin), ctypes.byref(fout),
+        _check_forward(L.lsr_forward_preprocess_async(ctypes.byref(st.c), ctypes.byref(fin), ctypes.byref(fout),
                                                       ctypes.c_void_p(geom.data_ptr()),
                                                       ctypes.c_void_p(count.data_ptr()),
                                                       ctypes.c_void_p(stream.cuda_stream)),
-                       "lsr_forward_preprocess_async")
-        except RuntimeError:
-            _dump_forward(raster_settings, inputs)
-            raise
+                       "lsr_forward_preprocess_async", raster_settings, inputs)
         pf = PendingForward(raster_settings, st, fin, inputs, geom, radii, None, device, H, W)
         pf.count_host, pf.stream = count, stream
         pf.counted = torch.cuda.Event()
         pf.counted.record(stream)
         return pf
     K = ctypes.c_int64(0)
-    try:
-        _lib.check(L.lsr_forward_preprocess(ctypes.byref(st.c), ctypes.byref(fin), ctypes.byref(fout),
+    _check_forward(L.lsr_forward_preprocess(ctypes.byref(st.c), ctypes.byref(fin), ctypes.byref(fout),
                                             ctypes.c_void_p(geom.data_ptr()), ctypes.byref(K),
-                                            ctypes.c_void_p(stream.cuda_stream)), "lsr_forward_preprocess")
-    except RuntimeError:
-        _dump_forward(raster_settings, inputs)
-        raise
+                                            ctypes.c_void_p(stream.cuda_stream)),
+                   "lsr_forward_preprocess", raster_settings, inputs)
     pf = PendingForward(raster_settings, st, fin, inputs, geom, radii, K.value, device, H, W)
     if binning:
         _run_binning(pf, stream)
@@ -239,14 +258,11 @@ def _run_binning(pf, stream):
     with torch.cuda.stream(stream):
         pf.binning = torch.empty(int(L.lsr_binning_bytes(K)), dtype=torch.uint8, device=device)
         pf.img = torch.empty(int(L.lsr_img_bytes(W, H)), dtype=torch.uint8, device=device)
-    try:
-        _lib.check(L.lsr_forward_binning(ctypes.byref(pf.settings.c), ctypes.byref(pf.fin),
+    _check_forward(L.lsr_forward_binning(ctypes.byref(pf.settings.c), ctypes.byref(pf.fin),
                                          ctypes.c_void_p(pf.geom.data_ptr()), ctypes.c_void_p(pf.binning.data_ptr()),
                                          ctypes.c_void_p(pf.img.data_ptr()), ctypes.c_int64(K),
-                                         ctypes.c_void_p(stream.cuda_stream)), "lsr_forward_binning")
-    except RuntimeError:
-        _dump_forward(pf.raster_settings, pf.inputs)
-        raise
+                                         ctypes.c_void_p(stream.cuda_stream)),
+                   "lsr_forward_binning", pf.raster_settings, pf.inputs)
     pf.ready = torch.cuda.Event()
     pf.ready.record(stream)               # render_native's stream waits for the binning
     pf.ready_stream = stream
@@ -336,42 +352,29 @@ def preprocess_views_native(raster_settings_list, means3D, opacities, shs=None, 
         fo.radii = r.data_ptr()
     k = n if (order_first is None or order_stream is None) else max(0, min(int(order_first), n))
     counts = torch.zeros(k, 2, dtype=torch.int32, pin_memory=True) if k > 0 else None
-    s_arr = (ctypes.POINTER(_lib.Settings) * n)(*[ctypes.pointer(x.c) for x in sts])
-    o_arr = (ctypes.POINTER(_lib.FwdOut) * n)(*[ctypes.pointer(fo) for fo in fouts])
-    g_arr = (ctypes.c_void_p * n)(*[g.data_ptr() for g in geoms])
-    try:
-        if tile_bucket:
-            for r0, r1, before in (row_chunks or [(0, P, None)]):
-                if before is not None:
-                    before()
-                _lib.check(L.lsr_forward_preprocess_views_tb_async(n, int(r0), int(r1), s_arr, ctypes.byref(fin), o_arr,
-                                                                   g_arr, ctypes.c_void_p(stream.cuda_stream)),
-                           "lsr_forward_preprocess_views_tb_async")
-            if k > 0:
-                _lib.check(L.lsr_forward_instance_scan_views_async(k, s_arr, ctypes.byref(fin), g_arr,
-                                                                   ctypes.c_void_p(counts.data_ptr()),
-                                                                   ctypes.c_void_p(stream.cuda_stream)),
-                           "lsr_forward_instance_scan_views_async")
-        elif row_chunks:
-            for r0, r1, before in row_chunks:
-                if before is not None:
-                    before()
-                _lib.check(L.lsr_forward_preprocess_views_rows_async(n, int(r0), int(r1), s_arr, ctypes.byref(fin),
-                                                                     o_arr, g_arr, ctypes.c_void_p(stream.cuda_stream)),
-                           "lsr_forward_preprocess_views_rows_async")
-            if k > 0:
-                _lib.check(L.lsr_forward_depth_order_views_async(k, s_arr, ctypes.byref(fin), g_arr,
-                                                                 ctypes.c_void_p(counts.data_ptr()),
-                                                                 ctypes.c_void_p(stream.cuda_stream)),
-                           "lsr_forward_depth_order_views_async")
-        else:
-            _lib.check(L.lsr_forward_preprocess_views_split_async(n, k, s_arr, ctypes.byref(fin), o_arr, g_arr,
-                                                                  ctypes.c_void_p(counts.data_ptr() if k else 0),
-                                                                  ctypes.c_void_p(stream.cuda_stream)),
-                       "lsr_forward_preprocess_views_split_async")
-    except RuntimeError:
-        _dump_forward(raster_settings_list[0], inputs)
-        raise
+    s_arr, o_arr, g_arr = _settings_array(sts), _struct_array(_lib.FwdOut, fouts), _ptr_array(geoms)
+    fi, stp = ctypes.byref(fin), ctypes.c_void_p(stream.cuda_stream)
+
+    def check(rc, what):
+        _check_forward(rc, what, raster_settings_list[0], inputs)
+
+    count_fn, count_what = ((L.lsr_forward_instance_scan_views_async, "lsr_forward_instance_scan_views_async")
+                            if tile_bucket else
+                            (L.lsr_forward_depth_order_views_async, "lsr_forward_depth_order_views_async"))
+    if tile_bucket or row_chunks:
+        rows_fn, rows_what = ((L.lsr_forward_preprocess_views_tb_async, "lsr_forward_preprocess_views_tb_async")
+                              if tile_bucket else
+                              (L.lsr_forward_preprocess_views_rows_async, "lsr_forward_preprocess_views_rows_async"))
+        for r0, r1, before in (row_chunks or [(0, P, None)]):
+            if before is not None:
+                before()
+            check(rows_fn(n, int(r0), int(r1), s_arr, fi, o_arr, g_arr, stp), rows_what)
+        if k > 0:
+            check(count_fn(k, s_arr, fi, g_arr, ctypes.c_void_p(counts.data_ptr()), stp), count_what)
+    else:
+        check(L.lsr_forward_preprocess_views_split_async(n, k, s_arr, fi, o_arr, g_arr,
+                                                         ctypes.c_void_p(counts.data_ptr() if k else 0), stp),
+              "lsr_forward_preprocess_views_split_async")
     ev = torch.cuda.Event()
     ev.record(stream)
     late = None
@@ -380,15 +383,8 @@ def preprocess_views_native(raster_settings_list, means3D, opacities, shs=None, 
         for g in geoms[k:]:
             g.record_stream(order_stream)
         counts_b = torch.zeros(n - k, 2, dtype=torch.int32, pin_memory=True)
-        fn, what = ((L.lsr_forward_instance_scan_views_async, "lsr_forward_instance_scan_views_async") if tile_bucket
-                    else (L.lsr_forward_depth_order_views_async, "lsr_forward_depth_order_views_async"))
-        try:
-            _lib.check(fn(n - k, (ctypes.POINTER(_lib.Settings) * (n - k))(*s_arr[k:]), ctypes.byref(fin),
-                          (ctypes.c_void_p * (n - k))(*g_arr[k:]), ctypes.c_void_p(counts_b.data_ptr()),
-                          ctypes.c_void_p(order_stream.cuda_stream)), what)
-        except RuntimeError:
-            _dump_forward(raster_settings_list[0], inputs)
-            raise
+        check(count_fn(n - k, _settings_array(sts[k:]), fi, _ptr_array(geoms[k:]), ctypes.c_void_p(counts_b.data_ptr()),
+                       ctypes.c_void_p(order_stream.cuda_stream)), count_what)
         ev_b = torch.cuda.Event()
         ev_b.record(order_stream)
         late = (counts_b, ev_b)
@@ -432,6 +428,47 @@ def _img_bytes(W, H):
     return _align(int(_lib.load().lsr_img_bytes(W, H)))
 
 
+def _view_arrays(views, *between):
+    """(settings array, &fin, *between, geom, binning, img and num_rendered arrays) of binned views
+    (PendingForward or RasterizerState) of the same Gaussians: the *_views entry points' argument run."""
+    return (_settings_array([v.settings for v in views]), ctypes.byref(views[0].fin), *between,
+            _ptr_array([v.geom for v in views]), _ptr_array([v.binning for v in views]),
+            _ptr_array([v.img for v in views]), _int64_array([v.num_rendered for v in views]))
+
+
+def _forward_outputs(pf):
+    """A view's colour, language and depth images on the current stream, and their lsr_fwd_out."""
+    H, W, C = pf.H, pf.W, pf.fin.C
+    color = torch.empty(3, H, W, dtype=torch.float32, device=pf.device)
+    lang_out = torch.empty(C, H, W, dtype=torch.float32, device=pf.device)
+    depth = torch.empty(1, H, W, dtype=torch.float32, device=pf.device)
+    fout = _lib.FwdOut()
+    fout.out_color, fout.out_language_feature = color.data_ptr(), _ptr(lang_out) if C > 0 else None
+    fout.radii, fout.out_depth = pf.radii.data_ptr(), depth.data_ptr()
+    return color, lang_out, depth, fout
+
+
+def _wait_for_binning(pf, stream, waited=None):
+    """`stream` waits for pf's binning event, once: not when the binning ran on `stream` (already
+    ordered; a wait idles the device) and not when `waited` has the (event, stream) pair (views
+    binned together share one event).  waited: the caller's set for one batch; None: a set kept on
+    the event itself, across calls."""
+    if pf.ready_stream is None or pf.ready_stream == stream:
+        return
+    if waited is None:
+        waited = getattr(pf.ready, "_lsr_waited_by", None)
+        if waited is None:
+            waited = set()
+            try:
+                pf.ready._lsr_waited_by = waited
+            except AttributeError:
+                pass
+    key = (id(pf.ready), stream.cuda_stream)
+    if key not in waited:
+        stream.wait_event(pf.ready)
+        waited.add(key)
+
+
 def binning_views_native(pendings, stream=None):
     """Resolve the deferred counts of preprocess_views_native's views (one host wait) and run their
     tile binning as one batch (lsr_forward_binning_views) on `stream` (default: theirs), so that
@@ -468,19 +505,10 @@ def binning_views_native(pendings, stream=None):
         off += sizes[2 * i]
         pf.img = ws[off:off + sizes[2 * i + 1]]
         off += sizes[2 * i + 1]
-    s_arr = (ctypes.POINTER(_lib.Settings) * n)(*[ctypes.pointer(pf.settings.c) for pf in pendings])
-    g_arr = (ctypes.c_void_p * n)(*[pf.geom.data_ptr() for pf in pendings])
-    b_arr = (ctypes.c_void_p * n)(*[pf.binning.data_ptr() for pf in pendings])
-    i_arr = (ctypes.c_void_p * n)(*[pf.img.data_ptr() for pf in pendings])
-    k_arr = (ctypes.c_int64 * n)(*[pf.num_rendered for pf in pendings])
     fn, what = ((L.lsr_forward_binning_views_tb, "lsr_forward_binning_views_tb") if tb
                 else (L.lsr_forward_binning_views, "lsr_forward_binning_views"))
-    try:
-        _lib.check(fn(n, s_arr, ctypes.byref(pendings[0].fin), g_arr, b_arr, i_arr, k_arr,
-                      ctypes.c_void_p(stream.cuda_stream)), what)
-    except RuntimeError:
-        _dump_forward(pendings[0].raster_settings, pendings[0].inputs)
-        raise
+    _check_forward(fn(n, *_view_arrays(pendings), ctypes.c_void_p(stream.cuda_stream)), what,
+                   pendings[0].raster_settings, pendings[0].inputs)
     ev = torch.cuda.Event()
     ev.record(stream)
     for pf in pendings:
@@ -494,28 +522,16 @@ def render_native(pending: PendingForward):
     if pending.tile_bucket and pending.binning is None:   # lsr_forward_render bins the sort path's way
         binning_views_native([pending], stream=torch.cuda.current_stream(pending.device))
     pending.resolve()
-    device, H, W, C = pending.device, pending.H, pending.W, pending.fin.C
+    device, H, W = pending.device, pending.H, pending.W
     stream = torch.cuda.current_stream(device)
     pending.geom.record_stream(stream)    # allocated on the preprocess stream, used from here on
     pending.radii.record_stream(stream)
-    color = torch.empty(3, H, W, dtype=torch.float32, device=device)
-    lang_out = torch.empty(C, H, W, dtype=torch.float32, device=device)
-    depth = torch.empty(1, H, W, dtype=torch.float32, device=device)
-    fout = _lib.FwdOut()
-    fout.out_color, fout.out_language_feature = color.data_ptr(), _ptr(lang_out) if C > 0 else None
-    fout.radii, fout.out_depth = pending.radii.data_ptr(), depth.data_ptr()
+    color, lang_out, depth, fout = _forward_outputs(pending)
     K = pending.num_rendered
     binned = pending.binning is not None
     if binned:
         binning, img = pending.binning, pending.img
-        if pending.ready_stream != stream:   # same stream: already ordered (a wait idles the device)
-            waited = getattr(pending.ready, "_lsr_waited_by", None)
-            if waited is None or stream.cuda_stream not in waited:   # views binned together share one event
-                stream.wait_event(pending.ready)
-                try:
-                    pending.ready._lsr_waited_by = (waited or set()) | {stream.cuda_stream}
-                except AttributeError:
-                    pass
+        _wait_for_binning(pending, stream)
         binning.record_stream(stream)
         img.record_stream(stream)
     else:
@@ -523,13 +539,10 @@ def render_native(pending: PendingForward):
         img = torch.empty(int(L.lsr_img_bytes(W, H)), dtype=torch.uint8, device=device)
     fn, what = (L.lsr_forward_composite, "lsr_forward_composite") if binned else (L.lsr_forward_render,
                                                                                    "lsr_forward_render")
-    try:
-        _lib.check(fn(ctypes.byref(pending.settings.c), ctypes.byref(pending.fin), ctypes.byref(fout),
+    _check_forward(fn(ctypes.byref(pending.settings.c), ctypes.byref(pending.fin), ctypes.byref(fout),
                       ctypes.c_void_p(pending.geom.data_ptr()), ctypes.c_void_p(binning.data_ptr()),
-                      ctypes.c_void_p(img.data_ptr()), ctypes.c_int64(K), _stream(device)), what)
-    except RuntimeError:
-        _dump_forward(pending.raster_settings, pending.inputs)
-        raise
+                      ctypes.c_void_p(img.data_ptr()), ctypes.c_int64(K), _stream(device)), what,
+                   pending.raster_settings, pending.inputs)
     state = RasterizerState(pending.settings, pending.inputs, pending.fin, pending.geom, binning, img, K, pending.radii)
     return color, lang_out, pending.radii, depth, state
 
@@ -549,8 +562,7 @@ def radii_max_native(radii, out, accumulate=False, stream=None):
     if out.dtype != torch.int32 or not out.is_contiguous():
         raise ValueError("radii_max_native: out must be a contiguous int32 tensor")
     stream = stream or torch.cuda.current_stream(out.device)
-    arr = (ctypes.c_void_p * len(rs))(*[r.data_ptr() for r in rs])
-    _lib.check(L.lsr_radii_max(P, len(rs), arr, ctypes.c_void_p(out.data_ptr()), 1 if accumulate else 0,
+    _lib.check(L.lsr_radii_max(P, len(rs), _ptr_array(rs), ctypes.c_void_p(out.data_ptr()), 1 if accumulate else 0,
                                ctypes.c_void_p(stream.cuda_stream)), "lsr_radii_max")
     return out
 
@@ -573,34 +585,16 @@ def render_views_native(pendings):
     for pf in pendings:
         if pf.device != device or (pf.H, pf.W) != (pendings[0].H, pendings[0].W):
             raise ValueError("render_views_native: the views must share the device and image size")
-        if pf.ready_stream is not None and pf.ready_stream != stream and id(pf.ready) not in waited:
-            stream.wait_event(pf.ready)   # one wait per binning batch (a wait idles the device)
-            waited.add(id(pf.ready))
+        _wait_for_binning(pf, stream, waited)   # one wait per binning batch
         for t in (pf.geom, pf.radii, pf.binning, pf.img):
             t.record_stream(stream)
-        H, W, C = pf.H, pf.W, pf.fin.C
-        color = torch.empty(3, H, W, dtype=torch.float32, device=device)
-        lang_out = torch.empty(C, H, W, dtype=torch.float32, device=device)
-        depth = torch.empty(1, H, W, dtype=torch.float32, device=device)
-        fout = _lib.FwdOut()
-        fout.out_color, fout.out_language_feature = color.data_ptr(), _ptr(lang_out) if C > 0 else None
-        fout.radii, fout.out_depth = pf.radii.data_ptr(), depth.data_ptr()
+        color, lang_out, depth, fout = _forward_outputs(pf)
         outs.append((color, lang_out, depth))
         fouts.append(fout)
-    n = len(pendings)
-    s_arr = (ctypes.POINTER(_lib.Settings) * n)(*[ctypes.pointer(pf.settings.c) for pf in pendings])
-    o_arr = (ctypes.POINTER(_lib.FwdOut) * n)(*[ctypes.pointer(f) for f in fouts])
-    vp = ctypes.c_void_p * n
-    try:
-        _lib.check(L.lsr_forward_composite_views(n, s_arr, ctypes.byref(pendings[0].fin), o_arr,
-                                                 vp(*[pf.geom.data_ptr() for pf in pendings]),
-                                                 vp(*[pf.binning.data_ptr() for pf in pendings]),
-                                                 vp(*[pf.img.data_ptr() for pf in pendings]),
-                                                 (ctypes.c_int64 * n)(*[pf.num_rendered for pf in pendings]),
-                                                 _stream(device)), "lsr_forward_composite_views")
-    except RuntimeError:
-        _dump_forward(pendings[0].raster_settings, pendings[0].inputs)
-        raise
+    _check_forward(L.lsr_forward_composite_views(len(pendings),
+                                                 *_view_arrays(pendings, _struct_array(_lib.FwdOut, fouts)),
+                                                 _stream(device)),
+                   "lsr_forward_composite_views", pendings[0].raster_settings, pendings[0].inputs)
     res = []
     for pf, (color, lang_out, depth) in zip(pendings, outs):
         state = RasterizerState(pf.settings, pf.inputs, pf.fin, pf.geom, pf.binning, pf.img, pf.num_rendered, pf.radii)
@@ -623,44 +617,11 @@ def backward_native(state: RasterizerState, grad_color, grad_lang=None, grad_dep
     accumulate=True they are added to.  deterministic=True selects the fixed-order reduction
     (bitwise reproducible gradients).  Returns the dict of gradient tensors."""
     L = _lib.load()
-    inp = state.inputs
-    means3D = inp["means3D"]
-    device = means3D.device
-    P, M, C = state.fin.P, state.fin.M, state.fin.C
-    H, W = state.settings.c.image_height, state.settings.c.image_width
-    need = need or {}
-
-    def buf(name, shape, wanted=True):
-        if not wanted:
-            return None
-        if out is not None and name in out and out[name] is not None:
-            return out[name]
-        return torch.zeros(shape, dtype=torch.float32, device=device) if accumulate else \
-            torch.empty(shape, dtype=torch.float32, device=device)
-
-    g = dict(
-        means3D=buf("means3D", (P, 3), need.get("means3D", True)),
-        means2D=buf("means2D", (P, 3), need.get("means2D", True)),
-        colors=buf("colors", (P, 3), need.get("colors", True)),
-        language_feature=buf("language_feature", (P, C), need.get("language_feature", True) and C > 0),
-        opacities=buf("opacities", (P, 1), need.get("opacities", True)),
-        cov3D=buf("cov3D", (P, 6), need.get("cov3D", True) and inp["cov3D_precomp"] is not None),
-        sh=buf("sh", (P, max(M, 1), 3), need.get("sh", True) and M > 0),
-        scales=buf("scales", (P, 3), need.get("scales", True) and inp["scales"] is not None),
-        rotations=buf("rotations", (P, 4), need.get("rotations", True) and inp["rotations"] is not None),
-    )
-    gc = grad_color.detach().to(torch.float32).contiguous() if grad_color is not None else \
-        torch.zeros(3, H, W, dtype=torch.float32, device=device)
-    gl = grad_lang.detach().to(torch.float32).contiguous() if (grad_lang is not None and C > 0) else None
-    gd = grad_depth.detach().to(torch.float32).contiguous() if grad_depth is not None else None
-    gin = _lib.BwdIn()
-    gin.dL_dout_color, gin.dL_dout_language_feature, gin.dL_dout_depth = gc.data_ptr(), _ptr(gl), _ptr(gd)
-    gin.deterministic = 1 if deterministic else 0
-    gout = _lib.BwdOut()
-    gout.dL_dmeans3D, gout.dL_dmeans2D, gout.dL_dcolors = _ptr(g["means3D"]), _ptr(g["means2D"]), _ptr(g["colors"])
-    gout.dL_dlanguage_feature, gout.dL_dopacity = _ptr(g["language_feature"]), _ptr(g["opacities"])
-    gout.dL_dcov3D, gout.dL_dsh = _ptr(g["cov3D"]), _ptr(g["sh"])
-    gout.dL_dscales, gout.dL_drotations = _ptr(g["scales"]), _ptr(g["rotations"])
+    device = state.inputs["means3D"].device
+    P, C = state.fin.P, state.fin.C
+    g = _grad_buffers(state, out, accumulate, need or {})
+    keep, gin = _bwd_in(state, grad_color, grad_lang, grad_depth, deterministic)   # keep: alive until enqueued
+    gout = _bwd_out(g)
     scratch = torch.empty(int(L.lsr_backward_bytes(P, state.num_rendered, C, 1 if deterministic else 0)),
                           dtype=torch.uint8, device=device)
     rc = L.lsr_backward(ctypes.byref(state.settings.c), ctypes.byref(state.fin), ctypes.byref(gin), ctypes.byref(gout),
@@ -669,7 +630,7 @@ def backward_native(state: RasterizerState, grad_color, grad_lang=None, grad_dep
                         ctypes.c_int64(state.num_rendered), ctypes.c_int32(1 if accumulate else 0), _stream(device))
     if rc != 0 and state.settings.c.debug:
         print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.")
-        torch.save(dict(grad_color=gc.cpu()), "snapshot_bw.dump")
+        torch.save(dict(grad_color=keep[0].cpu()), "snapshot_bw.dump")
     _lib.check(rc, "lsr_backward")
     return g
 
@@ -697,59 +658,11 @@ def backward_views_native(states, grad_colors, grad_langs=None, grad_depths=None
         if s.inputs["means3D"].data_ptr() != inp["means3D"].data_ptr():
             raise ValueError("all views must render the same Gaussians")
     device = inp["means3D"].device
-    P, M, C = st0.fin.P, st0.fin.M, st0.fin.C
-    need = need or {}
-    grad_langs = grad_langs or [None] * n
-    grad_depths = grad_depths or [None] * n
-
-    def buf(name, shape, wanted=True):
-        if not wanted:
-            return None
-        if out is not None and name in out and out[name] is not None:
-            return out[name]
-        return torch.zeros(shape, dtype=torch.float32, device=device) if accumulate else \
-            torch.empty(shape, dtype=torch.float32, device=device)
-
-    g = dict(
-        means3D=buf("means3D", (P, 3), need.get("means3D", True)),
-        means2D=buf("means2D", (P, 3), need.get("means2D", True)),
-        colors=buf("colors", (P, 3), need.get("colors", True)),
-        language_feature=buf("language_feature", (P, C), need.get("language_feature", True) and C > 0),
-        opacities=buf("opacities", (P, 1), need.get("opacities", True)),
-        cov3D=buf("cov3D", (P, 6), need.get("cov3D", True) and inp["cov3D_precomp"] is not None),
-        sh=buf("sh", (P, max(M, 1), 3), need.get("sh", True) and M > 0),
-        scales=buf("scales", (P, 3), need.get("scales", True) and inp["scales"] is not None),
-        rotations=buf("rotations", (P, 4), need.get("rotations", True) and inp["rotations"] is not None),
-    )
-    keep = []
-    gins = []
-    for v, s in enumerate(states):
-        H, W = s.settings.c.image_height, s.settings.c.image_width
-        gc = grad_colors[v].detach().to(torch.float32).contiguous() if grad_colors[v] is not None else \
-            torch.zeros(3, H, W, dtype=torch.float32, device=device)
-        gl = grad_langs[v].detach().to(torch.float32).contiguous() if (grad_langs[v] is not None and C > 0) else None
-        gd = grad_depths[v].detach().to(torch.float32).contiguous() if grad_depths[v] is not None else None
-        keep += [gc, gl, gd]
-        gi = _lib.BwdIn()
-        gi.dL_dout_color, gi.dL_dout_language_feature, gi.dL_dout_depth = gc.data_ptr(), _ptr(gl), _ptr(gd)
-        gi.deterministic = 0
-        gins.append(gi)
-    gout = _lib.BwdOut()
-    gout.dL_dmeans3D, gout.dL_dmeans2D, gout.dL_dcolors = _ptr(g["means3D"]), _ptr(g["means2D"]), _ptr(g["colors"])
-    gout.dL_dlanguage_feature, gout.dL_dopacity = _ptr(g["language_feature"]), _ptr(g["opacities"])
-    gout.dL_dcov3D, gout.dL_dsh = _ptr(g["cov3D"]), _ptr(g["sh"])
-    gout.dL_dscales, gout.dL_drotations = _ptr(g["scales"]), _ptr(g["rotations"])
-    SP = ctypes.POINTER(_lib.Settings)
-    BP = ctypes.POINTER(_lib.BwdIn)
-    s_arr = (SP * n)(*[ctypes.pointer(s.settings.c) for s in states])
-    g_arr = (BP * n)(*[ctypes.pointer(gi) for gi in gins])
-    vp = ctypes.c_void_p * n
-    geom = vp(*[s.geom.data_ptr() for s in states])
-    binning = vp(*[s.binning.data_ptr() for s in states])
-    img = vp(*[s.img.data_ptr() for s in states])
-    K = (ctypes.c_int64 * n)(*[s.num_rendered for s in states])
-    _lib.check(L.lsr_backward_views(n, s_arr, ctypes.byref(st0.fin), g_arr, ctypes.byref(gout), geom, binning, img,
-                                    K, 1 if accumulate else 0, _stream(device)), "lsr_backward_views")
+    g = _grad_buffers(st0, out, accumulate, need or {})
+    keeps, gins = _bwd_in_views(states, grad_colors, grad_langs, grad_depths)   # keeps: alive until enqueued
+    gout = _bwd_out(g)
+    _lib.check(L.lsr_backward_views(n, *_view_arrays(states, _struct_array(_lib.BwdIn, gins), ctypes.byref(gout)),
+                                    1 if accumulate else 0, _stream(device)), "lsr_backward_views")
     for s in states:
         s.composited = True
     return g
@@ -775,14 +688,7 @@ def backward_composite_native(state: RasterizerState, grad_color, grad_lang=None
                            "accumulated in the forward's workspace, so a second run would double them")
     device = state.inputs["means3D"].device
     P, C = state.fin.P, state.fin.C
-    H, W = state.settings.c.image_height, state.settings.c.image_width
-    gc = grad_color.detach().to(torch.float32).contiguous() if grad_color is not None else \
-        torch.zeros(3, H, W, dtype=torch.float32, device=device)
-    gl = grad_lang.detach().to(torch.float32).contiguous() if (grad_lang is not None and C > 0) else None
-    gd = grad_depth.detach().to(torch.float32).contiguous() if grad_depth is not None else None
-    gi = _lib.BwdIn()
-    gi.dL_dout_color, gi.dL_dout_language_feature, gi.dL_dout_depth = gc.data_ptr(), _ptr(gl), _ptr(gd)
-    gi.deterministic = 0
+    keep, gi = _bwd_in(state, grad_color, grad_lang, grad_depth)
     if dL_dlanguage is not None and (dL_dlanguage.shape != (P, C) or not dL_dlanguage.is_contiguous()):
         raise ValueError("dL_dlanguage must be a contiguous [P, C] tensor")
     _lib.check(L.lsr_backward_composite(ctypes.byref(state.settings.c), ctypes.byref(state.fin), ctypes.byref(gi),
@@ -791,7 +697,7 @@ def backward_composite_native(state: RasterizerState, grad_color, grad_lang=None
                                         ctypes.c_void_p(state.img.data_ptr()),
                                         ctypes.c_int64(state.num_rendered), _stream(device)), "lsr_backward_composite")
     state.composited = True
-    return CompositeGrad(state, (gc, gl, gd))
+    return CompositeGrad(state, keep)
 
 
 def backward_composite_views_native(states, grad_colors, grad_langs=None, grad_depths=None,
@@ -810,34 +716,15 @@ def backward_composite_views_native(states, grad_colors, grad_langs=None, grad_d
     st0 = states[0]
     device = st0.inputs["means3D"].device
     P, C = st0.fin.P, st0.fin.C
-    n = len(states)
-    grad_langs = grad_langs or [None] * n
-    grad_depths = grad_depths or [None] * n
     if dL_dlanguage is not None and (dL_dlanguage.shape != (P, C) or not dL_dlanguage.is_contiguous()):
         raise ValueError("dL_dlanguage must be a contiguous [P, C] tensor")
-    gins, keeps = [], []
-    for v, s in enumerate(states):
+    for s in states:
         if s.inputs["means3D"].data_ptr() != st0.inputs["means3D"].data_ptr():
             raise ValueError("all views must render the same Gaussians")
-        H, W = s.settings.c.image_height, s.settings.c.image_width
-        gc = grad_colors[v].detach().to(torch.float32).contiguous() if grad_colors[v] is not None else \
-            torch.zeros(3, H, W, dtype=torch.float32, device=device)
-        gl = grad_langs[v].detach().to(torch.float32).contiguous() if (grad_langs[v] is not None and C > 0) else None
-        gd = grad_depths[v].detach().to(torch.float32).contiguous() if grad_depths[v] is not None else None
-        gi = _lib.BwdIn()
-        gi.dL_dout_color, gi.dL_dout_language_feature, gi.dL_dout_depth = gc.data_ptr(), _ptr(gl), _ptr(gd)
-        gi.deterministic = 0
-        gins.append(gi)
-        keeps.append((gc, gl, gd))
-    s_arr = (ctypes.POINTER(_lib.Settings) * n)(*[ctypes.pointer(s.settings.c) for s in states])
-    g_arr = (ctypes.POINTER(_lib.BwdIn) * n)(*[ctypes.pointer(gi) for gi in gins])
-    vp = ctypes.c_void_p * n
-    _lib.check(L.lsr_backward_composite_views(n, s_arr, ctypes.byref(st0.fin), g_arr,
-                                              _ptr(dL_dlanguage if C > 0 else None),
-                                              vp(*[s.geom.data_ptr() for s in states]),
-                                              vp(*[s.binning.data_ptr() for s in states]),
-                                              vp(*[s.img.data_ptr() for s in states]),
-                                              (ctypes.c_int64 * n)(*[s.num_rendered for s in states]),
+    keeps, gins = _bwd_in_views(states, grad_colors, grad_langs, grad_depths)
+    _lib.check(L.lsr_backward_composite_views(len(states),
+                                              *_view_arrays(states, _struct_array(_lib.BwdIn, gins),
+                                                            _ptr(dL_dlanguage if C > 0 else None)),
                                               _stream(device)), "lsr_backward_composite_views")
     for s in states:
         s.composited = True
@@ -867,10 +754,8 @@ def backward_preprocess_views_native(parts, out=None, accumulate=False, need=Non
     need["language_feature"] = False
     g = _grad_buffers(st0, out, accumulate, need)
     gout = _bwd_out(g)
-    SP = ctypes.POINTER(_lib.Settings)
-    vp = ctypes.c_void_p * n
-    s_arr = (SP * n)(*[ctypes.pointer(p_.state.settings.c) for p_ in parts])
-    geoms = vp(*[p_.state.geom.data_ptr() for p_ in parts])
+    s_arr = _settings_array([p_.state.settings for p_ in parts])
+    geoms = _ptr_array([p_.state.geom for p_ in parts])
     if row_chunks is None:
         _lib.check(L.lsr_backward_preprocess_views(n, s_arr, ctypes.byref(st0.fin), ctypes.byref(gout), geoms,
                                                    1 if accumulate else 0, _stream(device)),
@@ -920,6 +805,30 @@ def _grad_buffers(state, out, accumulate, need):
     )
 
 
+def _bwd_in(state, grad_color, grad_lang, grad_depth, deterministic=False):
+    """A view's upstream gradients as fp32 contiguous tensors (zeros for a missing colour gradient;
+    the language gradient only when C > 0) and the lsr_bwd_in over them: ((gc, gl, gd), gin).  The
+    caller keeps the tensors alive until the backward is enqueued."""
+    device = state.inputs["means3D"].device
+    H, W = state.settings.c.image_height, state.settings.c.image_width
+    gc = grad_color.detach().to(torch.float32).contiguous() if grad_color is not None else \
+        torch.zeros(3, H, W, dtype=torch.float32, device=device)
+    gl = grad_lang.detach().to(torch.float32).contiguous() if (grad_lang is not None and state.fin.C > 0) else None
+    gd = grad_depth.detach().to(torch.float32).contiguous() if grad_depth is not None else None
+    gin = _lib.BwdIn()
+    gin.dL_dout_color, gin.dL_dout_language_feature, gin.dL_dout_depth = gc.data_ptr(), _ptr(gl), _ptr(gd)
+    gin.deterministic = 1 if deterministic else 0
+    return (gc, gl, gd), gin
+
+
+def _bwd_in_views(states, grad_colors, grad_langs, grad_depths):
+    """_bwd_in per view (grad_langs / grad_depths may be None): ([kept tensors], [lsr_bwd_in])."""
+    n = len(states)
+    grad_langs, grad_depths = grad_langs or [None] * n, grad_depths or [None] * n
+    pairs = [_bwd_in(s, grad_colors[v], grad_langs[v], grad_depths[v]) for v, s in enumerate(states)]
+    return [k for k, _ in pairs], [gi for _, gi in pairs]
+
+
 def _bwd_out(g):
     gout = _lib.BwdOut()
     gout.dL_dmeans3D, gout.dL_dmeans2D, gout.dL_dcolors = _ptr(g["means3D"]), _ptr(g["means2D"]), _ptr(g["colors"])
@@ -927,6 +836,16 @@ def _bwd_out(g):
     gout.dL_dcov3D, gout.dL_dsh = _ptr(g["cov3D"]), _ptr(g["sh"])
     gout.dL_dscales, gout.dL_drotations = _ptr(g["scales"]), _ptr(g["rotations"])
     return gout
+
+
+def _language_image_and_shapes(raster_settings, color, lang, lang_in, sh, opacities):
+    """What both autograd functions keep of a view's forward: its language image (zeros when the
+    language channels are off) and the input shapes the backward restores."""
+    if not raster_settings.include_feature and lang_in is not None and lang_in.numel() > 0:
+        # base stages: the caller passes zeros [P, hiddendim] and discards the output
+        lang = torch.zeros((lang_in.shape[-1],) + tuple(color.shape[1:]), dtype=color.dtype, device=color.device)
+    return lang, dict(sh=None if sh is None else sh.shape, opacities=opacities.shape,
+                      lang=None if lang_in is None else lang_in.shape)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -937,14 +856,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             raster_settings, means3D, opacities, shs=sh, colors_precomp=colors_precomp,
             language_feature=language_feature_precomp if raster_settings.include_feature else None,
             scales=scales, rotations=rotations, cov3D_precomp=cov3Ds_precomp)
-        if not raster_settings.include_feature and language_feature_precomp is not None \
-                and language_feature_precomp.numel() > 0:
-            # base stages: the caller passes zeros [P, hiddendim] and discards the output
-            lang = torch.zeros((language_feature_precomp.shape[-1],) + tuple(color.shape[1:]),
-                               dtype=color.dtype, device=color.device)
+        lang, ctx.shapes = _language_image_and_shapes(raster_settings, color, lang, language_feature_precomp, sh,
+                                                      opacities)
         ctx.state = state
-        ctx.shapes = dict(sh=None if sh is None else sh.shape, opacities=opacities.shape,
-                          lang=None if language_feature_precomp is None else language_feature_precomp.shape)
         ctx.include_feature = raster_settings.include_feature
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)
@@ -1005,12 +919,9 @@ class _RasterizeViews(torch.autograd.Function):
         ctx.views = []
         for v, (rs, pf) in enumerate(zip(settings_list, pfs)):
             color, lang, radii, depth, state = render_native(pf)
-            lang_in, sh, op = flat[9 * v + 4], flat[9 * v + 2], flat[9 * v + 5]
-            if not rs.include_feature and lang_in is not None and lang_in.numel() > 0:
-                lang = torch.zeros((lang_in.shape[-1],) + tuple(color.shape[1:]), dtype=color.dtype,
-                                   device=color.device)
-            ctx.views.append((state, dict(sh=None if sh is None else sh.shape, opacities=op.shape,
-                                          lang=None if lang_in is None else lang_in.shape), rs.include_feature))
+            lang, shapes = _language_image_and_shapes(rs, color, lang, flat[9 * v + 4], flat[9 * v + 2],
+                                                      flat[9 * v + 5])
+            ctx.views.append((state, shapes, rs.include_feature))
             outs += [color, lang, radii, depth]
             radii_all.append(radii)
         ctx.mark_non_differentiable(*radii_all)

@@ -99,6 +99,153 @@ def test_train_glue_argument_checks():
     assert lib.lsr_repeat_rows(0, None, 4, 2, None) == 0 and lib.lsr_sum_row_blocks(1, rt, 0, 2, None) == 0
 
 
+def test_rasterizer_argument_checks():
+    """The rasterizer's entry points (include/lsr.h) refuse bad batches with LSR_EINVAL and their
+    message, every view validated before anything touches a device, and accept P = 0 as no work."""
+    import ctypes
+    from diff_gaussian_rasterization import _lib
+    lib = _lib.load()
+    err = lambda: lib.lsr_last_error().decode()
+    FAKE = 64                                                  # never dereferenced: every call returns early
+
+    def settings(W=64, H=48, scale=1.0, feature=1):
+        s = _lib.Settings()
+        s.image_width, s.image_height, s.tanfovx, s.tanfovy = W, H, 0.5, 0.5
+        s.bg = s.viewmatrix = s.projmatrix = s.campos = FAKE
+        s.scale_modifier, s.sh_degree, s.include_feature = scale, 0, feature
+        return s
+
+    def views(*ss):
+        return (ctypes.POINTER(_lib.Settings) * len(ss))(*[ctypes.pointer(s) for s in ss])
+
+    def structs(cls, n, **fields):
+        objs = [cls(**fields) for _ in range(n)]
+        return (ctypes.POINTER(cls) * n)(*[ctypes.pointer(o) for o in objs]), objs
+
+    def refused(rc, text):
+        assert rc == 1 and text in err(), (rc, err())          # LSR_EINVAL
+
+    fin = _lib.FwdIn()
+    fin.P, fin.M, fin.C = 1000, 0, 0
+    fin.means3D = fin.opacities = fin.colors_precomp = fin.scales = fin.rotations = FAKE
+    fi = ctypes.byref(fin)
+    same = views(settings(), settings())
+    sizes = views(settings(), settings(W=80))
+    scales = views(settings(), settings(scale=2.0))
+    features = views(settings(), settings(feature=0))
+    vp = (ctypes.c_void_p * 2)(FAKE, FAKE)
+    K = (ctypes.c_int64 * 2)(10, 10)
+    hc = ctypes.c_void_p(FAKE)
+    outs, _o = structs(_lib.FwdOut, 2, out_color=FAKE, out_depth=FAKE, radii=FAKE)
+    no_radii, _n = structs(_lib.FwdOut, 2, out_color=FAKE, out_depth=FAKE)
+    gins, _g = structs(_lib.BwdIn, 2, dL_dout_color=FAKE)
+    det, _d = structs(_lib.BwdIn, 2, dL_dout_color=FAKE, deterministic=1)
+    gout = ctypes.byref(_lib.BwdOut())
+
+    # every batched entry point as f(n_views, settings array): the other arguments valid
+    batched = {
+        "lsr_forward_preprocess_views_async":
+            lambda n, s: lib.lsr_forward_preprocess_views_async(n, s, fi, outs, vp, hc, None),
+        "lsr_forward_preprocess_views_split_async":
+            lambda n, s: lib.lsr_forward_preprocess_views_split_async(n, n, s, fi, outs, vp, hc, None),
+        "lsr_forward_preprocess_views_rows_async":
+            lambda n, s: lib.lsr_forward_preprocess_views_rows_async(n, 0, 1000, s, fi, outs, vp, None),
+        "lsr_forward_preprocess_views_tb_async":
+            lambda n, s: lib.lsr_forward_preprocess_views_tb_async(n, 0, 1000, s, fi, outs, vp, None),
+        "lsr_forward_depth_order_views_async":
+            lambda n, s: lib.lsr_forward_depth_order_views_async(n, s, fi, vp, hc, None),
+        "lsr_forward_instance_scan_views_async":
+            lambda n, s: lib.lsr_forward_instance_scan_views_async(n, s, fi, vp, hc, None),
+        "lsr_forward_binning_views": lambda n, s: lib.lsr_forward_binning_views(n, s, fi, vp, vp, vp, K, None),
+        "lsr_forward_binning_views_tb": lambda n, s: lib.lsr_forward_binning_views_tb(n, s, fi, vp, vp, vp, K, None),
+        "lsr_forward_composite_views":
+            lambda n, s: lib.lsr_forward_composite_views(n, s, fi, outs, vp, vp, vp, K, None),
+        "lsr_backward_composite_views":
+            lambda n, s: lib.lsr_backward_composite_views(n, s, fi, gins, None, vp, vp, vp, K, None),
+        "lsr_backward_preprocess_views": lambda n, s: lib.lsr_backward_preprocess_views(n, s, fi, gout, vp, 0, None),
+        "lsr_backward_preprocess_views_rows":
+            lambda n, s: lib.lsr_backward_preprocess_views_rows(n, s, fi, gout, vp, 0, 0, 1000, None),
+        "lsr_backward_views": lambda n, s: lib.lsr_backward_views(n, s, fi, gins, gout, vp, vp, vp, K, 0, None),
+    }
+    own_words = ("lsr_backward_preprocess_views", "lsr_backward_preprocess_views_rows", "lsr_backward_views")
+    for name, f in batched.items():
+        refused(f(0, same), "n_views must be >= 1" if name in own_words else "n_views >= 1 and the per-view arrays")
+        refused(f(2, None), "null argument" if name in own_words else "the per-view arrays are required")
+    for name in ("lsr_forward_preprocess_views_async", "lsr_forward_preprocess_views_split_async",
+                 "lsr_forward_preprocess_views_rows_async", "lsr_forward_preprocess_views_tb_async",
+                 "lsr_forward_depth_order_views_async", "lsr_forward_instance_scan_views_async"):
+        refused(batched[name](2, sizes), "share the image size, sh_degree and scale_modifier")
+        refused(batched[name](2, scales), "share the image size, sh_degree and scale_modifier")
+    for name in ("lsr_forward_binning_views", "lsr_forward_binning_views_tb"):
+        refused(batched[name](2, sizes), "batched views must share the image size")
+    for name in ("lsr_forward_composite_views", "lsr_backward_composite_views", "lsr_backward_views"):
+        refused(batched[name](2, sizes), "share the image size and include_feature")
+        refused(batched[name](2, features), "share the image size and include_feature")
+    for name in ("lsr_backward_preprocess_views", "lsr_backward_preprocess_views_rows", "lsr_backward_views"):
+        refused(batched[name](2, scales), "all views must share scale_modifier")
+    null_view = (ctypes.c_void_p * 2)(FAKE, None)
+    refused(lib.lsr_forward_depth_order_views_async(2, same, fi, null_view, hc, None), "geom workspaces are required")
+    refused(lib.lsr_forward_binning_views(2, same, fi, vp, vp, null_view, K, None), "workspaces are required")
+    refused(lib.lsr_forward_binning_views_tb(2, same, fi, vp, null_view, vp, K, None), "workspaces are required")
+    refused(lib.lsr_backward_preprocess_views(2, same, fi, gout, null_view, 0, None),
+            "geom workspace is required for every")
+
+    # rows, ordered views, outputs and counts
+    refused(lib.lsr_forward_preprocess_views_rows_async(2, 128, 1000, same, fi, outs, vp, None),
+            "row0 a multiple of 256")
+    refused(lib.lsr_forward_preprocess_views_tb_async(2, 128, 1000, same, fi, outs, vp, None), "row0 a multiple of 256")
+    refused(lib.lsr_forward_preprocess_views_rows_async(2, 0, 1001, same, fi, outs, vp, None), "row0 <= row1 <= P")
+    refused(lib.lsr_backward_preprocess_views_rows(2, same, fi, gout, vp, 0, 128, 100, None),
+            "row_begin must be a multiple")
+    refused(lib.lsr_backward_preprocess_views_rows(2, same, fi, gout, vp, 0, 768, 256, None), "must lie inside [0, P)")
+    refused(lib.lsr_forward_preprocess_views_split_async(2, 3, same, fi, outs, vp, hc, None),
+            "0 <= n_ordered <= n_views")
+    refused(lib.lsr_forward_preprocess_views_split_async(2, 1, same, fi, outs, vp, None, None),
+            "0 <= n_ordered <= n_views")
+    refused(lib.lsr_forward_preprocess_views_split_async(2, 2, same, fi, no_radii, vp, hc, None),
+            "radii output is required")
+    refused(lib.lsr_forward_preprocess_views_rows_async(2, 0, 1000, same, fi, no_radii, vp, None),
+            "radii output is required")
+    refused(lib.lsr_forward_preprocess_async(same[0], fi, no_radii[0], hc, hc, None), "radii output is required")
+    refused(lib.lsr_forward_preprocess_async(same[0], fi, outs[0], hc, None, None), "geom workspace and host_count are")
+    refused(lib.lsr_forward_preprocess_async(same[0], fi, outs[0], None, hc, None), "geom workspace and host_count are")
+    refused(lib.lsr_forward_preprocess(same[0], fi, outs[0], hc, None, None), "geom workspace and num_rendered are")
+    refused(lib.lsr_forward_preprocess_views_async(2, same, fi, outs, vp, None, None), "host_counts is required")
+    refused(lib.lsr_forward_depth_order_views_async(2, same, fi, vp, None, None), "host_counts is required")
+    refused(lib.lsr_forward_instance_scan_views_async(2, same, fi, vp, None, None), "host_counts is required")
+    refused(lib.lsr_forward_composite_views(2, same, fi, structs(_lib.FwdOut, 2, radii=FAKE)[0], vp, vp, vp, K, None),
+            "color and depth outputs are required")
+    refused(lib.lsr_backward_composite_views(2, same, fi, structs(_lib.BwdIn, 2)[0], None, vp, vp, vp, K, None),
+            "dL_dout_color is required")
+    refused(lib.lsr_backward_composite_views(2, same, fi, det, None, vp, vp, vp, K, None),
+            "the split backward reduces with float atomics")
+    refused(lib.lsr_backward_views(2, same, fi, det, gout, vp, vp, vp, K, 0, None),
+            "lsr_backward_views reduces with float atomics")
+
+    # P = 0: nothing to do, the counts are zeroed on the host
+    fin.P = 0
+    counts = (ctypes.c_uint32 * 4)(7, 7, 7, 7)
+    cp = ctypes.c_void_p(ctypes.addressof(counts))
+
+    def zeroed(rc, n=4):
+        assert rc == 0 and list(counts) == [0] * n + [7] * (4 - n), (rc, err(), list(counts))
+        counts[:] = [7, 7, 7, 7]
+
+    zeroed(lib.lsr_forward_preprocess_async(same[0], fi, outs[0], hc, cp, None), 2)
+    zeroed(lib.lsr_forward_preprocess_views_async(2, same, fi, outs, vp, cp, None))
+    zeroed(lib.lsr_forward_preprocess_views_split_async(2, 1, same, fi, outs, vp, cp, None), 2)
+    zeroed(lib.lsr_forward_depth_order_views_async(2, same, fi, vp, cp, None))
+    zeroed(lib.lsr_forward_instance_scan_views_async(2, same, fi, vp, cp, None))
+    assert lib.lsr_forward_preprocess_views_rows_async(2, 0, 0, same, fi, outs, vp, None) == 0
+    assert lib.lsr_forward_preprocess_views_tb_async(2, 0, 0, same, fi, outs, vp, None) == 0
+    assert lib.lsr_backward(same[0], fi, gins[0], gout, hc, hc, hc, hc, 0, 0, None) == 0
+    assert lib.lsr_backward_composite(same[0], fi, gins[0], None, hc, hc, hc, 0, None) == 0
+    assert lib.lsr_backward_composite_views(2, same, fi, gins, None, vp, vp, vp, K, None) == 0
+    assert lib.lsr_backward_preprocess_views(2, same, fi, gout, vp, 0, None) == 0
+    assert lib.lsr_backward_preprocess_views_rows(2, same, fi, gout, vp, 0, 0, 0, None) == 0
+    assert lib.lsr_backward_views(2, same, fi, gins, gout, vp, vp, vp, K, 0, None) == 0
+
+
 def test_settings_validation_messages():
     """Upstream's exactly-one-of errors are raised before anything touches a device."""
     import torch

@@ -136,6 +136,74 @@ def test_empty_and_all_culled():
         assert float(depth.abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("P,culled", [(0, False), (5, True), (2048, False), (2049, False)])
+def test_deferred_count_equals_forward(P, culled):
+    """The single view's deferred instance count (lsr_forward_preprocess_async, read from pinned
+    memory by render_native) at the sizes where its delivery changes shape: no Gaussians, none
+    visible, and one scan tile (2048) against the two-tile scan (2049).  Same images, radii and
+    num_rendered as the synchronous forward, bit for bit."""
+    sc, cam = small_case(P=max(P, 1), W=96, H=64, C=3, seed=40 + P % 7)
+    if P == 0:
+        sc = synthetic.Scene(*(t[:0] for t in (sc.means3D, sc.scales, sc.rotations, sc.opacities, sc.shs, sc.lang)))
+    if culled:
+        sc.means3D[:, 2] = -1.0
+    dev = sc.to("cuda")
+    rs = raster_settings(cam)
+    kw = dict(shs=dev.shs, language_feature=dev.lang, scales=dev.scales, rotations=dev.rotations)
+    ref = dgr.forward_native(rs, dev.means3D, dev.opacities, **kw)
+    pf = dgr.preprocess_native(rs, dev.means3D, dev.opacities, defer_count=True, **kw)
+    assert pf.num_rendered is None and pf.counted is not None
+    got = dgr.render_native(pf)
+    assert got[4].num_rendered == ref[4].num_rendered
+    assert (ref[4].num_rendered == 0) == (P == 0 or culled)
+    for name, x, y in zip(("color", "language", "radii", "depth"), ref[:4], got[:4]):
+        assert x.shape == y.shape and torch.equal(x, y), name
+
+
+@pytest.mark.parametrize("n", [1, 8, 9])
+def test_phase_launch_counts(n):
+    """One set of launches per 8 views in every phase of the batched path (lsr.h), counted by the
+    library's phase timers; a single view's forward_native + backward_native runs each phase once
+    and the fused preprocess backward instead of the views one."""
+    from diff_gaussian_rasterization import _lib
+    C = 6
+    sc, _ = small_case(P=3000, W=96, H=64, C=C, seed=12, big_frac=0.05)
+    dev = sc.to("cuda")
+    rss = [raster_settings(c, bg=(0.3, 0.6, 0.9)) for c in synthetic.camera_batch(9, 96, 64, seed=12)[:n]]
+    kw = dict(scales=dev.scales, rotations=dev.rotations, shs=dev.shs, language_feature=dev.lang)
+    g = torch.Generator(device="cpu").manual_seed(4)
+    gcs = [torch.randn(3, 64, 96, generator=g).cuda() for _ in rss]
+    gls = [torch.randn(C, 64, 96, generator=g).cuda() for _ in rss]
+    forward = ("preprocess", "depth_sort", "instance_scan", "emit", "tile_sort", "render_fwd")
+    try:
+        _lib.profile_enable(True)
+        pfs = dgr.preprocess_views_native(rss, dev.means3D, dev.opacities, **kw)
+        dgr.binning_views_native(pfs)
+        res = dgr.render_views_native(pfs)
+        assert all(r[4].num_rendered > 0 for r in res)   # no empty view: every phase has work
+        dgr.backward_views_native([r[4] for r in res], gcs, gls)
+        torch.cuda.synchronize()
+        batch = {k: v[1] for k, v in _lib.profile_read().items()}
+        single = None
+        if n == 1:
+            _lib.profile_enable(True)
+            *_, st = dgr.forward_native(rss[0], dev.means3D, dev.opacities, **kw)
+            assert st.num_rendered > 0
+            dgr.backward_native(st, gcs[0], gls[0])
+            torch.cuda.synchronize()
+            single = {k: v[1] for k, v in _lib.profile_read().items()}
+    finally:
+        _lib.profile_enable(False)
+    sets = (n + 7) // 8
+    for k in forward + ("render_bwd", "preprocess_bwd_views"):
+        assert batch[k] == sets, (k, batch)
+    assert batch["preprocess_bwd"] == 0, batch
+    if single is not None:
+        for k in forward + ("render_bwd", "preprocess_bwd"):
+            assert single[k] == 1, (k, single)
+        assert single["preprocess_bwd_views"] == 0, single
+
+
 def test_sh_degrees():
     for deg in range(4):
         sc, cam = small_case(P=800, W=64, H=48, C=0, seed=10 + deg)
