@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("LSR_LIBRARY", os.path.join(_PKG, "build", "liblsr.so"
 c_float_p = ctypes.c_void_p  # device pointers are passed as opaque addresses
 API_VERSION = 4               # LSR_API_VERSION of the include/lsr.h these structs mirror
 DEFORM_API_VERSION = 3        # LSR_DEFORM_API_VERSION of include/lsr_deform.h (DeformNet, DeformGrads)
+QUERY_API_VERSION = 1         # LSR_QUERY_API_VERSION of include/lsr_query.h (Decoder)
 
 
 class Settings(ctypes.Structure):
@@ -89,8 +90,18 @@ class RowTensor(ctypes.Structure):
                 ("zero_from", ctypes.c_int64)]
 
 
+class Decoder(ctypes.Structure):
+    """include/lsr_query.h lsr_decoder"""
+    _fields_ = [("n_layers", ctypes.c_int32), ("dims", ctypes.c_int32 * 9), ("weight", ctypes.c_void_p * 8),
+                ("bias", ctypes.c_void_p * 8)]
+
+
 ADAM_MAX_GROUPS = 16        # LSR_ADAM_MAX_GROUPS
 GATHER_MAX_TENSORS = 32     # LSR_GATHER_MAX_TENSORS
+QUERY_MAX_LAYERS = 8        # LSR_QUERY_MAX_LAYERS
+QUERY_MAX_PHRASES = 64      # LSR_QUERY_MAX_PHRASES
+QUERY_MAX_WIDTH = 512       # LSR_QUERY_MAX_WIDTH
+QUERY_MAX_INPUT = 32        # LSR_QUERY_MAX_INPUT
 
 _vp = ctypes.c_void_p
 SIGNATURES = {
@@ -217,6 +228,11 @@ SIGNATURES = {
     "lsr_deform_backward_scratch_bytes": (ctypes.c_int64, [ctypes.POINTER(DeformNet), ctypes.c_int32]),
     "lsr_deform_backward": (ctypes.c_int, [ctypes.POINTER(DeformNet), ctypes.c_void_p, ctypes.c_int32]
                             + [ctypes.c_void_p] * 14 + [ctypes.POINTER(DeformGrads), ctypes.c_void_p, ctypes.c_void_p]),
+    "lsr_query_require_api": (ctypes.c_int, [ctypes.c_int32]),
+    "lsr_query_relevancy": (ctypes.c_int, [ctypes.POINTER(Decoder), ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64,
+                                           ctypes.c_int32, _vp, ctypes.c_int32, _vp, ctypes.c_float, _vp, _vp]),
+    "lsr_query_decode": (ctypes.c_int, [ctypes.POINTER(Decoder), ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64,
+                                        _vp, _vp]),
     "lsr_profile_read": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
                                         ctypes.c_int32]),
 }
@@ -256,7 +272,8 @@ def load():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
-        if lib.lsr_require_api(API_VERSION) != 0 or lib.lsr_deform_require_api(DEFORM_API_VERSION) != 0:
+        if (lib.lsr_require_api(API_VERSION) != 0 or lib.lsr_deform_require_api(DEFORM_API_VERSION) != 0
+                or lib.lsr_query_require_api(QUERY_API_VERSION) != 0):
             raise ImportError(f"{path}: {lib.lsr_last_error().decode()} (rebuild it: make -C 4dlangsplat_amd/csrc)")
         _LIB = lib
     return _LIB

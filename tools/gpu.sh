@@ -17,6 +17,7 @@
 #   deform_ab  deformation bench (DEFORM_ARGS) + a short configs[4] loop per VARIANTS ("cur name ..." library variants,
 #              or "name:VAR=val[,VAR2=val2]" environment variants), REPS rounds
 #   race       tools/deform_race.py (deformation backward repeatability) per library VARIANTS
+#   query      tools/bench_query.py: the fused open-vocabulary query against its torch expression (QUERY_ARGS)
 #   side       the side benches: configs[1] stand-in (bench_render), configs[4] loop (bench_train_loop)
 # Library variants are built on the CPU beforehand (tools/build_variants.sh, tools/ab_base.sh).
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
@@ -122,6 +123,10 @@ for task in "$@"; do
             > "$O/race_$v.log" 2>&1 || { tail -5 "$O/race_$v.log"; fail "race $v"; }
         echo "$v:"; grep -E "^run" "$O/race_$v.log" | cut -c1-150
       done ;;
+    query)
+      timeout -k 10 300 python tools/bench_query.py --out "$O/bench_query.json" ${QUERY_ARGS:-} > "$O/bench_query.log" 2>&1 \
+          || { tail -5 "$O/bench_query.log"; fail query; }
+      tail -c 1800 "$O/bench_query.log"; echo ;;
     side)
       timeout -k 10 300 python tools/bench_render.py > "$O/bench_render.log" 2>&1 || { tail -5 "$O/bench_render.log"; fail render; }
       tail -c 800 "$O/bench_render.log"; echo
