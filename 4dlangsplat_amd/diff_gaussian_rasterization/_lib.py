@@ -90,6 +90,12 @@ class RowTensor(ctypes.Structure):
                 ("zero_from", ctypes.c_int64)]
 
 
+class SegView(ctypes.Structure):
+    """include/lsr_train.h lsr_seg_view"""
+    _fields_ = [("image", ctypes.c_void_p), ("d_image", ctypes.c_void_p), ("seg", ctypes.c_void_p),
+                ("table", ctypes.c_void_p), ("n_seg", ctypes.c_int32)]
+
+
 class Decoder(ctypes.Structure):
     """include/lsr_query.h lsr_decoder"""
     _fields_ = [("n_layers", ctypes.c_int32), ("dims", ctypes.c_int32 * 9), ("weight", ctypes.c_void_p * 8),
@@ -98,6 +104,7 @@ class Decoder(ctypes.Structure):
 
 ADAM_MAX_GROUPS = 16        # LSR_ADAM_MAX_GROUPS
 GATHER_MAX_TENSORS = 32     # LSR_GATHER_MAX_TENSORS
+SEG_LOSS_MAX_VIEWS = 8      # lsr_seg_loss_views' V
 QUERY_MAX_LAYERS = 8        # LSR_QUERY_MAX_LAYERS
 QUERY_MAX_PHRASES = 64      # LSR_QUERY_MAX_PHRASES
 QUERY_MAX_WIDTH = 512       # LSR_QUERY_MAX_WIDTH
@@ -122,6 +129,11 @@ SIGNATURES = {
     "lsr_l1_loss_views": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp]),
     "lsr_l1_loss_views_backward": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp,
                                                   _vp]),
+    "lsr_seg_loss_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32] * 4),
+    "lsr_seg_loss_views": (ctypes.c_int, [ctypes.c_int32] * 4 + [ctypes.POINTER(SegView), ctypes.c_float,
+                                          ctypes.c_float, ctypes.c_int32, _vp, _vp, _vp]),
+    "lsr_seg_loss_views_backward": (ctypes.c_int, [ctypes.c_int32] * 4 + [ctypes.POINTER(SegView), ctypes.c_float,
+                                                   ctypes.c_float, ctypes.c_int32, _vp, _vp, _vp]),
     "lsr_repeat_rows": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(RowTensor), ctypes.c_int64, ctypes.c_int32, _vp]),
     "lsr_sum_row_blocks": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(RowTensor), ctypes.c_int64, ctypes.c_int32,
                                           _vp]),

@@ -32,6 +32,9 @@ training_setup's lang branch (scene/gaussian_model.py:226-270):
   them, as the reference's requires_grad_(False) parameters.  The renders' coff (discrete fields)
   is collected as train.py:245-247 collects it; the reference computes no loss from it.
   Densification statistics are gathered in the 'base' stages only (train.py:388).
+  The supervision comes either as the dense gt_lang / lang_mask tensors of Camera.get_language_feature
+  or, with lang_sup=, as one language_supervision.SegmentSupervision per view (the files' segment map
+  and feature table), from which the same loss is computed fused, the dense tensors never built.
 """
 from __future__ import annotations
 
@@ -233,30 +236,43 @@ class TrainStep:
                              g(tr["rotation"]), max_sh_degree=self.sh_degree, active_sh_degree=self.sh_degree,
                              deformation=self.field)
 
+    @staticmethod
+    def _one_supervision_form(gt_lang, lang_mask, lang_sup) -> None:
+        if lang_sup is not None and (gt_lang is not None or lang_mask is not None):
+            raise ValueError("give the language supervision either as gt_lang with lang_mask or as lang_sup, not both")
+
     def loss(self, outs, gts: Optional[torch.Tensor], gt_lang: Optional[torch.Tensor] = None,
-             lang_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+             lang_mask: Optional[torch.Tensor] = None, lang_sup: Optional[Sequence] = None) -> torch.Tensor:
         """The stage's loss over the views' render outputs (train.py:272-296).  Base stages: L1 of the
         images against gts [V, 3(+), H, W].  'lang' stages: gt_lang [V, C, H, W], lang_mask [V, 1, H, W]
         (the reference trains them one view at a time, batch_size 1, where its cat over views is this
-        stack)."""
+        stack), or lang_sup: one language_supervision.SegmentSupervision per view, the same loss fused
+        from the segment maps and feature tables (segment_lang_loss)."""
+        self._one_supervision_form(gt_lang, lang_mask, lang_sup)
         if not self.lang_stage:
             return l1_loss_views([o["render"] for o in outs], gts)
-        if gt_lang is None or lang_mask is None:
-            raise ValueError("a 'lang' stage needs gt_lang and lang_mask")
-        lang = torch.stack([o["language_feature_image"] for o in outs])
-        a, b = lang * lang_mask, gt_lang * lang_mask
-        loss = self.lam * (a - b).abs().mean()
-        if self.addcosloss:
-            loss = loss + self.beta * (1 - torch.nn.functional.cosine_similarity(a, b, dim=-1).mean())
+        if lang_sup is not None:
+            from language_supervision import segment_lang_loss
+            loss = segment_lang_loss([o["language_feature_image"] for o in outs], lang_sup, self.lam, self.beta,
+                                     self.addcosloss)
+        else:
+            if gt_lang is None or lang_mask is None:
+                raise ValueError("a 'lang' stage needs gt_lang and lang_mask")
+            lang = torch.stack([o["language_feature_image"] for o in outs])
+            a, b = lang * lang_mask, gt_lang * lang_mask
+            loss = self.lam * (a - b).abs().mean()
+            if self.addcosloss:
+                loss = loss + self.beta * (1 - torch.nn.functional.cosine_similarity(a, b, dim=-1).mean())
         if self.joint_train:
             images = torch.stack([o["render"] for o in outs])
             loss = loss + (images - gts[:, :3]).abs().mean()
         return loss
 
     def forward_backward(self, cams: Sequence, gts: Optional[torch.Tensor], gt_lang: Optional[torch.Tensor] = None,
-                         lang_mask: Optional[torch.Tensor] = None):
+                         lang_mask: Optional[torch.Tensor] = None, lang_sup: Optional[Sequence] = None):
         """Render every view, the stage's loss, loss.backward() (train.py:242-339).  Leaves the
         gradients in the trainer's parameters' .grad and the field's grads; returns (loss, outs)."""
+        self._one_supervision_form(gt_lang, lang_mask, lang_sup)
         if self.field is not None:
             self.field.zero_grad()
         sc = self.scene()
@@ -265,19 +281,22 @@ class TrainStep:
         else:
             outs = [render(cam, sc, self.bg, stage=self.stage) for cam in cams]
         self.coff = [o["coff"] for o in outs if o.get("coff") is not None]
-        loss = self.loss(outs, gts, gt_lang, lang_mask)
+        loss = self.loss(outs, gts, gt_lang, lang_mask, lang_sup)
         loss.backward()
         return loss, outs
 
     def __call__(self, cams: Sequence, gts: Optional[torch.Tensor], iteration: Optional[int] = None,
-                 gt_lang: Optional[torch.Tensor] = None, lang_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 gt_lang: Optional[torch.Tensor] = None, lang_mask: Optional[torch.Tensor] = None,
+                 lang_sup: Optional[Sequence] = None) -> torch.Tensor:
         """One iteration over the views `cams` with ground-truth images gts [V, 3, H, W] (and, in
-        the 'lang' stages, language features gt_lang [V, C, H, W] with masks lang_mask [V, 1, H, W]).
+        the 'lang' stages, language features gt_lang [V, C, H, W] with masks lang_mask [V, 1, H, W],
+        or lang_sup: one SegmentSupervision per view).
         Returns the loss (a device scalar; no host synchronisation here unless `densify` makes one)."""
+        self._one_supervision_form(gt_lang, lang_mask, lang_sup)
         tr = self.trainer
         self.iteration = self.iteration + 1 if iteration is None else iteration
         self.update_learning_rate(self.iteration)
-        loss, outs = self.forward_backward(cams, gts, gt_lang, lang_mask)
+        loss, outs = self.forward_backward(cams, gts, gt_lang, lang_mask, lang_sup)
         collect = getattr(self.densify, "collect_stats", None)
         # train.py:388: while iteration < densify_until_iter, in the 'base' stages
         if "base" in self.stage and (collect is None or collect(self.iteration)):

@@ -19,6 +19,8 @@
  *       -> lsr_activate, lsr_activate_backward
  *   - the base stages' L1 image loss                         train.py:272-276
  *       -> lsr_l1_loss_views, lsr_l1_loss_views_backward
+ *   - the 'lang' stages' masked L1 (+ cosine) loss against table[seg]   train.py:287-292, scene/cameras.py:92-118
+ *       -> lsr_seg_loss_views, lsr_seg_loss_views_backward
  *
  * Conventions as lsr.h: device pointers, float32 unless stated, contiguous rows; the library
  * allocates nothing (plans take a workspace of lsr_train_workspace_bytes(P)); every launch on
@@ -130,6 +132,36 @@ int lsr_l1_loss_views(int32_t V, int64_t n, const float *const *images, const fl
                       float *loss, void *workspace, void *stream);
 int lsr_l1_loss_views_backward(int32_t V, int64_t n, const float *const *images, const float *gt,
                                int64_t gt_view_stride, const float *d_loss, float *const *d_images, void *stream);
+
+/* The 'lang' stages' loss (train.py:287-292, utils/loss_utils.py:20-27) straight from the supervision files'
+ * contents (scene/cameras.py:92-118), the dense ground truth never built.  One view: */
+typedef struct lsr_seg_view {
+    const float *image;    /* [C, H, W] the rendered language image */
+    float *d_image;        /* [C, H, W] its gradient: written by the backward, ignored by the forward */
+    const int32_t *seg;    /* [H, W] segment of each pixel; labelled iff 0 <= seg < n_seg, any other value
+                              (the reference's -1, anything >= n_seg) is unlabelled and never used as an index */
+    const float *table;    /* [n_seg, C] the segments' features */
+    int32_t n_seg;
+} lsr_seg_view;
+/* Over V <= 8 views of one shape, with m the labelled mask, t = table[seg], a = x m, b = t m, N = V C H W:
+ *   L1   = sum |a - b| / N
+ *   cos  = mean over (v, c, h) of  sum_w a b / (max(|a|_w, 1e-8) max(|b|_w, 1e-8))
+ *          (cos_loss's dim = -1 is the width axis: one similarity per image row and channel; 0 for a row
+ *          without labelled pixels)
+ *   loss = lam L1 (+ beta (1 - cos) when with_cos), one device float.
+ * Every partial sum is added in a fixed order (no atomics: two calls give the same bits).  workspace >=
+ * lsr_seg_loss_workspace_bytes(V, C, H, W) (-1 on invalid sizes), 16-byte aligned; with with_cos the forward leaves the rows'
+ * (a.b, |a|^2, |b|^2) there and the backward of the same call reads them (it needs no workspace otherwise).
+ * The backward writes every element of d_image:
+ *   m (sign(x - t) ((d_loss lam) (1 / N)) - (d_loss beta / (V C H)) d cos / d a),  +0 where unlabelled;
+ * its L1 part is PyTorch's mul / mean / abs backward bit for bit, and d cos / d a has no |a| term where
+ * |a| <= 1e-8 (the clamp's constant branch).  16-byte loads and stores when W % 4 == 0 and every image, gradient
+ * and map is 16-byte aligned, scalar ones otherwise. */
+int64_t lsr_seg_loss_workspace_bytes(int32_t V, int32_t C, int32_t H, int32_t W);
+int lsr_seg_loss_views(int32_t V, int32_t C, int32_t H, int32_t W, const lsr_seg_view *views, float lam, float beta,
+                       int32_t with_cos, float *loss, void *workspace, void *stream);
+int lsr_seg_loss_views_backward(int32_t V, int32_t C, int32_t H, int32_t W, const lsr_seg_view *views, float lam,
+                                float beta, int32_t with_cos, const float *d_loss, void *workspace, void *stream);
 
 /* The render path's activations over P rows in one launch (gaussian_renderer/__init__.py:191-193,
  * gaussian_model.py:38-46; replaces torch.exp / torch.nn.functional.normalize / torch.sigmoid and

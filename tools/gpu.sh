@@ -18,6 +18,8 @@
 #              or "name:VAR=val[,VAR2=val2]" environment variants), REPS rounds
 #   race       tools/deform_race.py (deformation backward repeatability) per library VARIANTS
 #   query      tools/bench_query.py: the fused open-vocabulary query against its torch expression (QUERY_ARGS)
+#   langloss   tools/bench_lang_loss.py: the fused 'lang' stage loss against its dense torch expression and the
+#              L1 kernels (LANGLOSS_ARGS)
 #   side       the side benches: configs[1] stand-in (bench_render), configs[4] loop (bench_train_loop)
 # Library variants are built on the CPU beforehand (tools/build_variants.sh, tools/ab_base.sh).
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
@@ -127,6 +129,10 @@ for task in "$@"; do
       timeout -k 10 300 python tools/bench_query.py --out "$O/bench_query.json" ${QUERY_ARGS:-} > "$O/bench_query.log" 2>&1 \
           || { tail -5 "$O/bench_query.log"; fail query; }
       tail -c 1800 "$O/bench_query.log"; echo ;;
+    langloss)
+      timeout -k 10 300 python tools/bench_lang_loss.py --out "$O/bench_lang_loss.json" ${LANGLOSS_ARGS:-} \
+          > "$O/bench_lang_loss.log" 2>&1 || { tail -5 "$O/bench_lang_loss.log"; fail langloss; }
+      tail -c 3000 "$O/bench_lang_loss.log"; echo ;;
     side)
       timeout -k 10 300 python tools/bench_render.py > "$O/bench_render.log" 2>&1 || { tail -5 "$O/bench_render.log"; fail render; }
       tail -c 800 "$O/bench_render.log"; echo
