@@ -109,6 +109,9 @@ QUERY_MAX_LAYERS = 8        # LSR_QUERY_MAX_LAYERS
 QUERY_MAX_PHRASES = 64      # LSR_QUERY_MAX_PHRASES
 QUERY_MAX_WIDTH = 512       # LSR_QUERY_MAX_WIDTH
 QUERY_MAX_INPUT = 32        # LSR_QUERY_MAX_INPUT
+SEGMENT_MAX_SCALE = 63      # LSR_SEGMENT_MAX_SCALE (include/lsr_segment.h)
+SEGMENT_MAX_SIDE = 16384    # LSR_SEGMENT_MAX_SIDE
+SEGMENT_STRATEGIES = {"point": 0, "mean": 1}   # LSR_SEGMENT_POINT, LSR_SEGMENT_MEAN
 
 _vp = ctypes.c_void_p
 SIGNATURES = {
@@ -245,6 +248,9 @@ SIGNATURES = {
                                            ctypes.c_int32, _vp, ctypes.c_int32, _vp, ctypes.c_float, _vp, _vp]),
     "lsr_query_decode": (ctypes.c_int, [ctypes.POINTER(Decoder), ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64,
                                         _vp, _vp]),
+    "lsr_segment_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32] * 3),
+    "lsr_segment": (ctypes.c_int, [ctypes.c_int32] * 3 + [_vp, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp,
+                                   ctypes.c_int32] + [_vp] * 8),
     "lsr_profile_read": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
                                         ctypes.c_int32]),
 }

@@ -10,6 +10,8 @@ vector is never written, only n_pos floats per pixel.
     rel = relevancy(sem_feat, dec, pos_embeds, neg_embeds)                 # [L, H, W, C] -> [L, n_pos, H, W]
     rel = relevancy(render_pkg["language_feature_image"], dec, pos, neg, layout="chw")   # no host round trip
 
+    seg = segment(rel, gt_masks)        # masks, level scores, chosen level and IoU per phrase (activate_stream)
+
 The embeddings are used as given (the reference normalises them in set_positives); there is no
 text encoder here.
 
@@ -19,6 +21,7 @@ dtype.  That fallback is the CPU implementation, and in float64 the yardstick of
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import glob
 import os
@@ -29,7 +32,7 @@ import torch
 
 from diff_gaussian_rasterization import _lib
 
-__all__ = ["LanguageDecoder", "relevancy", "query_frames"]
+__all__ = ["LanguageDecoder", "relevancy", "query_frames", "Segmentation", "segment", "segment_frames"]
 
 
 class LanguageDecoder:
@@ -235,3 +238,171 @@ def query_frames(level_dirs, decoder, pos_embeds, neg_embeds, out_dir, rescale="
         np.save(path, rel.float().cpu().numpy())
         written.append(path)
     return written
+
+
+Segmentation = collections.namedtuple(
+    "Segmentation", ["blended", "mask_raw", "mask", "score", "level", "chosen_mask", "inter", "union", "iou",
+                     "chosen_iou"], defaults=[None, None, None, None])
+Segmentation.__doc__ = """What segment() returns.  For rel [L, n_pos, H, W]: blended float, mask_raw and mask
+bool, all [L, n_pos, H, W]; score [L, n_pos]; level [n_pos] int64, the level with the greatest score;
+chosen_mask [n_pos, H, W], mask at that level.  With annotations also inter, union (int64) and iou
+[L, n_pos] and chosen_iou [n_pos]; None without.  For rel [n_pos, H, W] the L axis is dropped."""
+
+
+def _segment_torch(v, gt, thresh, scale, strategy):
+    """activate_stream's lines (eval/eval.py:172-276) and smooth_cuda on [M, H, W] maps as torch ops in
+    v's dtype.  gt: [G, H, W] bool or None, map m uses gt[m % G]."""
+    F = torch.nn.functional
+    M = v.shape[0]
+    per_map = lambda x: x.reshape(M, -1)
+    a = F.avg_pool2d(v[:, None], scale, 1, scale // 2, count_include_pad=False)[:, 0]
+    b = 0.5 * (a + v)
+    o = b - per_map(b).min(dim=1).values[:, None, None]
+    o = o / (per_map(o).max(dim=1).values[:, None, None] + 1e-9)
+    o = o * 2.0 + (-1.0)
+    o = torch.clip(o, 0, 1)
+    raw = o > thresh
+    # smooth_cuda: AvgPool2d(7, 1, 3, count_include_pad=False)(raw) > 0.5 as the integer test 2 ones > valid
+    ones = F.avg_pool2d(raw.to(v.dtype)[:, None], 7, 1, 3, divisor_override=1)[:, 0]
+    valid = F.avg_pool2d(torch.ones_like(v[:1])[:, None], 7, 1, 3, divisor_override=1)[:, 0]
+    mask = 2 * ones > valid
+    if strategy == "point":
+        score = per_map(b).max(dim=1).values
+    else:                                              # the mean of b over raw, summed in double; 0 where raw is empty
+        cnt = per_map(raw).sum(dim=1)
+        tot = per_map(torch.where(raw, b.double(), torch.zeros((), dtype=torch.float64, device=v.device))).sum(dim=1)
+        score = torch.where(cnt > 0, tot / cnt.clamp(min=1), torch.zeros_like(tot)).to(v.dtype)
+    inter = union = None
+    if gt is not None:
+        g = gt[torch.arange(M, device=v.device) % gt.shape[0]]
+        inter = per_map(g & mask).sum(dim=1)
+        union = per_map(g | mask).sum(dim=1)
+    return b, raw, mask, score, inter, union
+
+
+@torch.no_grad()
+def segment(rel, gt_masks=None, thresh=0.4, scale=29, strategy="point"):
+    """Relevancy maps to masks, level scores and IoU (eval/eval.py activate_stream with smooth_cuda; the
+    contract is spelled out in include/lsr_segment.h).  rel: [L, n_pos, H, W] or [n_pos, H, W], not
+    modified.  gt_masks: [n_pos, H, W] bool or uint8 (non-zero is inside), or None.  thresh is
+    --mask_tresh, scale the smoothing window (odd, 1 ... 63), strategy "point" (score = max of the
+    blended map) or "mean" (its mean over mask_raw, 0 where that is empty).  Returns a Segmentation."""
+    if rel.dim() not in (3, 4):
+        raise ValueError(f"rel must be [L, n_pos, H, W] or [n_pos, H, W], got {tuple(rel.shape)}")
+    if not rel.dtype.is_floating_point:
+        raise ValueError(f"rel must be a floating-point tensor, got {rel.dtype}")
+    if int(scale) != scale or scale % 2 == 0 or not 1 <= scale <= _lib.SEGMENT_MAX_SCALE:
+        raise ValueError(f"scale must be odd and in 1 ... {_lib.SEGMENT_MAX_SCALE}, got scale = {scale}")
+    if strategy not in _lib.SEGMENT_STRATEGIES:
+        raise ValueError(f'strategy must be "point" or "mean", got {strategy!r}')
+    scale = int(scale)
+    levels = rel.detach() if rel.dim() == 4 else rel.detach()[None]
+    L, n_pos, H, W = levels.shape
+    if L < 1:
+        raise ValueError(f"rel has no levels: {tuple(rel.shape)}")
+    if not (1 <= H <= _lib.SEGMENT_MAX_SIDE and 1 <= W <= _lib.SEGMENT_MAX_SIDE):
+        raise ValueError(f"rel's H and W must be in 1 ... {_lib.SEGMENT_MAX_SIDE}, got {tuple(rel.shape)}")
+    gt = None
+    if gt_masks is not None:
+        if tuple(gt_masks.shape) != (n_pos, H, W):
+            raise ValueError(f"gt_masks must be [n_pos, H, W] = {(n_pos, H, W)} to go with rel "
+                             f"{tuple(rel.shape)}, got {tuple(gt_masks.shape)}")
+        if gt_masks.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"gt_masks must be bool or uint8, got {gt_masks.dtype}")
+        if gt_masks.device != rel.device:
+            raise ValueError(f"gt_masks is on {gt_masks.device} but rel is on {rel.device}")
+        gt = gt_masks.detach().contiguous()
+    M = L * n_pos
+    maps = levels.reshape(M, H, W).contiguous()
+    native = rel.dtype == torch.float32 and rel.device.type == "cuda"
+    if not native or M == 0:
+        b, raw, mask, score, inter, union = _segment_torch(maps, None if gt is None else gt != 0, float(thresh), scale,
+                                                           strategy)
+    else:
+        dev = rel.device
+        lib = _lib.load()
+        ws_bytes = lib.lsr_segment_workspace_bytes(M, H, W)
+        if ws_bytes < 0:
+            _lib.check(1, "lsr_segment_workspace_bytes")
+        b = torch.empty(M, H, W, dtype=torch.float32, device=dev)
+        raw8 = torch.empty(M, H, W, dtype=torch.uint8, device=dev)
+        mask8 = torch.empty(M, H, W, dtype=torch.uint8, device=dev)
+        score = torch.empty(M, dtype=torch.float32, device=dev)
+        inter = union = None
+        gt8 = None
+        if gt is not None:
+            gt8 = gt.view(torch.uint8) if gt.dtype == torch.bool else gt
+            inter = torch.empty(M, dtype=torch.int64, device=dev)
+            union = torch.empty(M, dtype=torch.int64, device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.lsr_segment(M, H, W, maps.data_ptr(), scale, float(thresh), _lib.SEGMENT_STRATEGIES[strategy],
+                                       ptr(gt8), n_pos, b.data_ptr(), raw8.data_ptr(), mask8.data_ptr(),
+                                       score.data_ptr(), ptr(inter), ptr(union), ws.data_ptr(), stream), "lsr_segment")
+        raw, mask = raw8.view(torch.bool), mask8.view(torch.bool)
+    shape = (L, n_pos)
+    b, raw, mask, score = b.reshape(*shape, H, W), raw.reshape(*shape, H, W), mask.reshape(*shape, H, W), score.reshape(shape)
+    level = torch.argmax(score, dim=0)                 # the lowest index wins ties, NaN counts as greatest
+    pick = torch.arange(n_pos, device=rel.device)
+    chosen_mask = mask[level, pick]
+    iou = chosen_iou = None
+    if gt is not None:
+        inter, union = inter.reshape(shape), union.reshape(shape)
+        iou = inter.to(rel.dtype) / union.to(rel.dtype)                    # 0 / 0 is NaN, as in the reference
+        chosen_iou = iou[level, pick]
+    if rel.dim() == 3:
+        b, raw, mask, score = b[0], raw[0], mask[0], score[0]
+        if gt is not None:
+            inter, union, iou = inter[0], union[0], iou[0]
+    return Segmentation(b, raw, mask, score, level, chosen_mask, inter, union, iou, chosen_iou)
+
+
+def segment_frames(level_dirs, decoder, pos_embeds, neg_embeds, out_dir, gt=None, **segment_kwargs):
+    """Segment every rendered frame: reads renders_npy/{idx:05d}.npy from each level's folder as
+    query_frames does (with its rescale="auto"), runs relevancy() and segment() on the decoder's
+    device, and writes out_dir/mask_npy/{idx:05d}.npy: the chosen masks, [n_pos, H, W] uint8.
+    gt: a mapping from frame name ("00007" or "00007.npy") to [n_pos, H, W] annotations (array or
+    tensor); frames without an entry are segmented but not scored.  Returns a dict: "paths", and with
+    gt also "table" {frame name: [(iou, level, scores [L]) per phrase]}, "phrase_iou" (each phrase's
+    mean over its frames) and "mean_iou" (their mean), as eval/eval.py:667-690 tabulates them."""
+    level_dirs = list(level_dirs)
+    if not level_dirs:
+        raise ValueError("no level folders given")
+    names = sorted(os.path.basename(p) for p in glob.glob(os.path.join(level_dirs[0], "renders_npy", "*.npy")))
+    if not names:
+        raise FileNotFoundError(f"no renders_npy/*.npy under {level_dirs[0]}")
+    dst = os.path.join(out_dir, "mask_npy")
+    os.makedirs(dst, exist_ok=True)
+    dev = decoder.device
+    pos, neg = pos_embeds.to(dev), neg_embeds.to(dev)
+    out = {"paths": []}
+    table = {}
+    for name in names:
+        frame = np.stack([np.load(os.path.join(d, "renders_npy", name)) for d in level_dirs])
+        x = torch.from_numpy(frame).float().to(dev)
+        if x.min() > 0:                                # eval/eval.py:604-605
+            x = x * 2.0 - 1
+        rel = relevancy(x, decoder, pos, neg, layout="hwc")
+        ann = None
+        if gt is not None:
+            ann = gt.get(name, gt.get(os.path.splitext(name)[0]))
+        if ann is not None:
+            ann = torch.as_tensor(ann)
+            ann = (ann if ann.dtype in (torch.bool, torch.uint8) else ann != 0).to(dev)
+        seg = segment(rel, ann, **segment_kwargs)
+        path = os.path.join(dst, name)
+        np.save(path, seg.chosen_mask.to(torch.uint8).cpu().numpy())
+        out["paths"].append(path)
+        if ann is not None:
+            iou, level, scores = seg.chosen_iou.cpu(), seg.level.cpu(), seg.score.cpu()
+            table[os.path.splitext(name)[0]] = [(float(iou[k]), int(level[k]), scores[:, k].tolist())
+                                                for k in range(iou.shape[0])]
+    if gt is not None:
+        out["table"] = table
+        n_pos = pos.shape[0]
+        rows = list(table.values())
+        out["phrase_iou"] = [sum(r[k][0] for r in rows) / len(rows) if rows else float("nan") for k in range(n_pos)]
+        out["mean_iou"] = sum(out["phrase_iou"]) / n_pos
+    return out
