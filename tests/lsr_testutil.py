@@ -109,11 +109,12 @@ def check_binning_against_upstream(state, ref_state, W, H):
 
 
 def run_native(scene, cam, bg=(1.0, 1.0, 1.0), include_feature=True, use_precomp_cov=False, colors_precomp=None,
-               sh_degree=3):
+               sh_degree=3, scale_modifier=1.0):
     dev = "cuda"
-    rs = raster_settings(cam, bg=bg, sh_degree=sh_degree, include_feature=include_feature)
+    rs = raster_settings(cam, bg=bg, sh_degree=sh_degree, include_feature=include_feature,
+                         scale_modifier=scale_modifier)
     kw = {}
-    if use_precomp_cov:
+    if use_precomp_cov:   # a precomputed covariance is taken as given: scale_modifier does not enter it
         kw["cov3D_precomp"] = torch.tensor(oracle.cov3d(scene.scales.numpy(), scene.rotations.numpy())).to(dev)
     else:
         kw["scales"], kw["rotations"] = scene.scales.to(dev), scene.rotations.to(dev)
@@ -126,8 +127,9 @@ def run_native(scene, cam, bg=(1.0, 1.0, 1.0), include_feature=True, use_precomp
 
 
 def run_oracle(scene, cam, bg=(1.0, 1.0, 1.0), include_feature=True, use_precomp_cov=False, colors_precomp=None,
-               sh_degree=3, nthreads=0):
-    s = oracle_settings(cam, bg=bg, sh_degree=sh_degree, include_feature=include_feature)
+               sh_degree=3, nthreads=0, scale_modifier=1.0):
+    s = oracle_settings(cam, bg=bg, sh_degree=sh_degree, include_feature=include_feature,
+                        scale_modifier=scale_modifier)
     kw = {}
     if use_precomp_cov:
         kw["cov3D_precomp"] = oracle.cov3d(scene.scales.numpy(), scene.rotations.numpy())
@@ -147,3 +149,60 @@ def grad_err(native, ref):
     ref = np.asarray(ref, np.float64)
     scale = max(np.abs(ref).max(), 1e-12)
     return float(np.abs(native - ref).max() / scale)
+
+
+GRAD_TOL = 1e-4
+# the gradient rows the compositor accumulates directly, by the oracle's names (abs_terms covers these)
+DIRECT_FIELDS = ("lang", "opacity", "means2D")
+# backward_native's names -> the oracle's
+NATIVE_TO_ORACLE = dict(means3D="means3D", means2D="means2D", colors="colors", opacities="opacity",
+                        language_feature="lang", cov3D="cov3D", sh="sh", scales="scales", rotations="rotations")
+
+
+def oracle_keyed(g):
+    """backward_native's dict (device tensors, None for the absent fields) under the oracle's names,
+    as float64 numpy."""
+    return {NATIVE_TO_ORACLE[k]: v.detach().double().cpu().numpy() for k, v in g.items() if v is not None}
+
+
+def grad_check(native, ref, abs_terms=None):
+    """Per-element check of gradients against a reference; both are dicts under the oracle's names
+    (oracle_keyed converts the native ones), and every field of `native` is checked.
+
+    Every field: grad_err <= GRAD_TOL, the tensor-wide contract.  The directly accumulated fields
+    (DIRECT_FIELDS), when `abs_terms` (the reference's backward(abs_terms=True)) has them, also per
+    element
+        |native - ref| <= 1e-4 |ref| + 1e-4 A
+    with A the sum of the magnitudes of the element's per-pixel terms: an element is held to the
+    rounding of what it was summed from, however small it is beside the tensor's largest (form and
+    coefficients: tests/test_headline_gpu.py).  No floor: an element with A = 0 must be exactly 0.
+    A non-finite value fails.
+
+    Returns (bad, stats): bad[field] describes the offences (empty dict: passed); stats[field] has
+    grad_err and, for the direct fields, max_err_over_A (over the elements with A > 0)."""
+    bad, stats = {}, {}
+    for key, n in native.items():
+        r = np.asarray(ref[key], np.float64)
+        n = np.asarray(n, np.float64).reshape(r.shape)
+        if r.size == 0:
+            continue
+        err = np.abs(n - r)
+        st = dict(grad_err=float(err.max() / max(np.abs(r).max(), 1e-12)))
+        off = {}
+        if not st["grad_err"] <= GRAD_TOL:
+            off["grad_err"] = st["grad_err"]
+        if abs_terms is not None and key in DIRECT_FIELDS:
+            A = np.asarray(abs_terms[key], np.float64).reshape(r.shape)
+            assert (A >= np.abs(r) * (1 - 1e-3) - 1e-30).all(), key      # |sum| <= sum |term|
+            pos = A > 0
+            st["max_err_over_A"] = float((err[pos] / A[pos]).max()) if pos.any() else 0.0
+            over = ~(err <= 1e-4 * np.abs(r) + 1e-4 * A)
+            if over.any():
+                idx = np.argwhere(over)
+                off["elements"] = int(over.sum())
+                off["first"] = [(tuple(int(i) for i in ix), float(n[tuple(ix)]), float(r[tuple(ix)]),
+                                 float(A[tuple(ix)])) for ix in idx[:6]]
+        stats[key] = st
+        if off:
+            bad[key] = off
+    return bad, stats

@@ -178,3 +178,68 @@ def test_backward_matches_finite_differences(seed):
             fd = (Lp - Lm) / (2 * eps)
             scale = max(1.0, abs(fd))
             assert abs(fd - ana[i, j]) <= 2e-4 * scale, (name, i, j, fd, ana[i, j])
+
+
+def _fd_branch(settings_kw, precomp=False, seed=3):
+    """test_backward_matches_finite_differences (same _fd_case, eps and tolerance) on the oracle's
+    other branches: settings_kw goes to oracle_settings; precomp renders from cov3D_precomp and
+    colors_precomp and checks their gradients instead of those of scales, rotations and SH."""
+    cam, inp = _fd_case(seed)
+    if precomp:
+        inp["cov3D"] = oracle.cov3d(inp.pop("scales"), inp.pop("rotations"), double=True)
+        inp["colors"] = np.random.default_rng(seed).uniform(0.2, 1.0, (len(inp["cov3D"]), 3))
+        del inp["shs"]
+    s = oracle_settings(cam, bg=(0.3, 0.6, 0.9), **settings_kw)
+    H, W, C = cam.image_height, cam.image_width, inp["lang"].shape[1]
+    rng = np.random.default_rng(100 + seed)
+    wts = (rng.normal(size=(3, H, W)), rng.normal(size=(C, H, W)), rng.normal(size=(H, W)))
+
+    def loss(x):
+        kw = dict(cov3D_precomp=x["cov3D"], colors_precomp=x["colors"]) if precomp else dict(
+            shs=x["shs"], scales=x["scales"], rotations=x["rotations"])
+        r = oracle.forward(s, x["means3D"], x["opacities"], lang=x["lang"], double=True, nthreads=1, **kw)
+        return (r.color * wts[0]).sum() + (r.lang * wts[1]).sum() + (r.depth[0] * wts[2]).sum(), r
+
+    L0, r = loss(inp)
+    g = r.backward(wts[0], wts[1], wts[2], nthreads=1)
+    eps = 1e-6
+    checks = {"means3D": "means3D", "opacities": "opacity", "lang": "lang"}
+    checks.update({"cov3D": "cov3D", "colors": "colors"} if precomp else
+                  {"scales": "scales", "rotations": "rotations", "shs": "sh"})
+    vis = np.nonzero(r.radii > 0)[0]
+    assert len(vis) > 10
+    checked = {name: 0 for name in checks}
+    for name, gname in checks.items():
+        base = inp[name]
+        ana = g[gname].reshape(base.shape[0], -1)
+        width = {"shs": 48, "cov3D": 6}.get(name, 4)
+        for i in vis[:8]:
+            for j in range(min(ana.shape[1], width)):
+                pert = {k: v.copy() for k, v in inp.items()}
+                flat = pert[name].reshape(base.shape[0], -1)
+                flat[i, j] += eps
+                Lp, rp = loss(pert)
+                flat[i, j] -= 2 * eps
+                Lm, rm = loss(pert)
+                if not (np.array_equal(rp.radii, r.radii) and np.array_equal(rm.radii, r.radii)):
+                    continue
+                fd = (Lp - Lm) / (2 * eps)
+                assert abs(fd - ana[i, j]) <= 2e-4 * max(1.0, abs(fd)), (name, i, j, fd, ana[i, j])
+                checked[name] += ana[i, j] != 0
+    assert all(n > 0 for n in checked.values()), checked   # every field had a non-zero gradient checked
+
+
+@pytest.mark.parametrize("scale_modifier", [0.7, 1.6])
+def test_backward_fd_scale_modifier(scale_modifier):
+    """scale_modifier enters cov3D and dL/dscale; no other test passes anything but 1."""
+    _fd_branch(dict(scale_modifier=scale_modifier))
+
+
+@pytest.mark.parametrize("sh_degree", [0, 1, 2])
+def test_backward_fd_sh_degree(sh_degree):
+    _fd_branch(dict(sh_degree=sh_degree))
+
+
+def test_backward_fd_precomputed():
+    """cov3D_precomp + colors_precomp: dL/dcov3D and dL/dcolors against finite differences."""
+    _fd_branch({}, precomp=True)
