@@ -16,7 +16,6 @@
 #include "lsr_common.h"
 #include "lsr_internal.h"
 #include <algorithm>
-#include <cstdlib>
 
 namespace lsr {
 
@@ -415,7 +414,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         const bool quat = hd == 2 && a.apply_rotation, coff = hd == 5;
         const bool resid_add = !quat && !coff;
         if (GRAD && resid_add) continue;
-#ifndef LSR_DEFORM_FWD_W2_WIDE
         if (nout <= 16) {                                            // block-uniform
             // a head of at most 16 outputs (pos, scales, rotations, opacity, coff): its output layer as
             // 16 x 16 x 32 MFMAs, one 16-row tile per wave (the 32-column tile of one wave computed
@@ -480,7 +478,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
             if (!resid_add) __syncthreads();   // s_q read before the next head's outputs
             continue;
         }
-#endif
         const bool owner = wave < (nout + 31) / 32;     // 1 N tile, or 2 for the 48 SH coefficients
         const int col = 32 * wave + (lane & 31), h = lane >> 5;
         // the residual inputs of this wave's outputs, loaded now so the head's first layer hides
@@ -576,10 +573,9 @@ __device__ __forceinline__ void w2_column(const __bf16* w2h, const __bf16* w2l, 
 // chain A_k = relu(H_k) (saved); per head, Z1 = A W1^T + b1, the gradient G of the head's output
 // (the upstream gradient, or for the quaternion product / the discrete combination their
 // per-Gaussian backward from the recomputed output), dZ1 = (G W2) * [Z1 > 0], and dA += dZ1 W1
-// (the heads' Z1 / dZ1 are not saved: k_head_wgrad recomputes them for the weight gradients), all
-// on the bf16 hi/lo MFMA of the forward with transposed weight
-// packs; then back through the chain, dH_k = dA_k * [H_k > 0] (saved), dA_{k-1} = dH_k W_k, and
-// dX = dH_0 W_0; and per Gaussian the HexPlane backward: each plane's sample gets dX times the
+// (the heads' Z1 / dZ1 are not saved: k_head_wgrad2 / k_head_wgrad3 recompute them for the weight
+// gradients), all on the bf16 hi/lo MFMA of the forward with transposed weight packs; then back
+// through the chain, dH_k = dA_k * [H_k > 0] (saved), dA_{k-1} = dH_k W_k, and dX = dH_0 W_0; and per Gaussian the HexPlane backward: each plane's sample gets dX times the
 // product of the other five planes of its scale, scattered to the 4 bilinear taps (float atomics
 // into a channel-last gradient copy: the 16 channels of a tap are one 64-byte segment), and the
 // coordinate gradient (zero where border padding clips) goes to d_means3D.
@@ -649,9 +645,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP ?
 
     DSTAMP(1);
     df32x16 dA[2] = {df32x16{}, df32x16{}};
-#ifdef LSR_DEFORM_ABL_NOHEADS   // timing ablation only (wrong gradients): the heads' share of phase A
-    if (a.P < 0)
-#endif
     for (int hd = 0; hd < DEF_HEADS; ++hd) {
         if (!((a.heads >> hd) & 1u)) continue;                       // block-uniform
         const int nout = head_out(a, hd);
@@ -662,7 +655,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP ?
         // phase A in the stamp build)
         constexpr int NJ = DN * 64 / 256;
         float gv[NJ];
-#ifndef LSR_DEFORM_SHG_LATE
         if (nout > DEF_SMALL_OUT) {                                  // block-uniform
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
@@ -670,7 +662,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP ?
                 gv[j] = (k < nout && g < a.P) ? G[(size_t)g * nout + k] : 0.0f;
             }
         }
-#endif
         // Z1 for this wave's 32 columns (its rows finish before the sync below)
         uint32_t zpos = 0;   // bit 16 mt + q: Z1 > 0 (the ReLU mask of dZ1; Z1 itself dies here)
         {
@@ -684,7 +675,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP ?
         }
         DSTAMP(2);
         if (nout <= DEF_SMALL_OUT) {                                 // block-uniform
-            // dZ1 = (G W2) [Z1 > 0] on the VALU from fp32 G rows (k_head_wgrad's small-output path)
+            // dZ1 = (G W2) [Z1 > 0] on the VALU from fp32 G rows (as k_head_wgrad3)
             // (loaded after Z1: issued before it, as the SH head's rows, measured 10.65-10.72 vs
             // 10.47-10.54 ms at 2M, 13 VGPRs spilled)
             if (tid < DN) {
@@ -727,35 +718,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP ?
         // gradient rows of this head's output, K padded to 64, in the buffer dZ1 takes next: every load
         // of the thread issued before the first conversion (a load-convert-store loop waited one memory
         // latency per row)
-#ifndef LSR_DEFORM_G_LOOP
-        {
-#ifdef LSR_DEFORM_SHG_LATE   // A/B: loaded here, after Z1
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const int i = tid + 256 * j, r = i >> 6, k = i & 63, g = g0 + r;
-                gv[j] = (k < nout && g < a.P) ? G[(size_t)g * nout + k] : 0.0f;
-            }
-#endif
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const int i = tid + 256 * j, r = i >> 6, k = i & 63;
-                __bf16 hi, lo;
-                dsplit(gv[j], hi, lo);
-                bh[r * DGP + k] = hi;
-                bl[r * DGP + k] = lo;
-            }
-        }
-#else   // A/B: the round-4 loop
-        for (int i = tid; i < DN * 64; i += 256) {
-            const int r = i >> 6, k = i & 63, g = g0 + r;
-            float v = 0.0f;
-            if (k < nout && g < a.P) v = G[(size_t)g * nout + k];
+        for (int j = 0; j < NJ; ++j) {
+            const int i = tid + 256 * j, r = i >> 6, k = i & 63;
             __bf16 hi, lo;
-            dsplit(v, hi, lo);
+            dsplit(gv[j], hi, lo);
             bh[r * DGP + k] = hi;
             bl[r * DGP + k] = lo;
         }
-#endif
         DSTAMP(10);        // SH head: G rows loaded and stored
         __syncthreads();   // G rows complete
         df32x16 d[2] = {df32x16{}, df32x16{}};
@@ -790,14 +760,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP ?
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int r = row_of(mt, q, hh), g = g0 + r;
-#ifndef LSR_DEFORM_CHAIN_RELOAD
-                // one layer: the mask from the registers (reloading A_0 put 32 dependent loads of rows
+                // one layer: the mask parked in s_apos (reloading A_0 put 32 dependent loads of rows
                 // this block had just written on the chain's critical path)
                 const bool on = DEEP ? (g < a.P && b.sA[k][(size_t)g * DWID + col] > 0.0f)
                                      : (g < a.P && ((s_apos[tid] >> (16 * mt + q)) & 1u));
-#else
-                const bool on = g < a.P && b.sA[k][(size_t)g * DWID + col] > 0.0f;   // this block wrote it
-#endif
                 const float v = on ? dA[mt][q] : 0.0f;
                 __bf16 hi, lo;
                 dsplit(v, hi, lo);
@@ -837,9 +803,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP ?
     float* const s_sw = reinterpret_cast<float*>(s_soff + 4 * 16 * 4);
 
     // ---- HexPlane backward: 4 threads per Gaussian, 4 channels each ----------------------------------
-#ifdef LSR_DEFORM_ABL_NOHEX   // timing ablation only (wrong gradients): the HexPlane backward's share
-    if (a.P < 0)
-#endif
     {
         const int gl = tid >> 2, q = tid & 3;
         const bool ok = g0 + gl < a.P;
@@ -930,9 +893,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP ?
                     for (int j = 0; j < 8; ++j) {
                         const int e = wave * 16 + 2 * j + half;
                         const float val = s_sdv[e * 17 + ch] * s_sw[e * 4 + tap];
-#ifndef LSR_DEFORM_ABL_NOTIME
                         if (val != 0.0f) atomicAdd(rp + s_soff[e * 4 + tap] + ch, val);
-#endif
                     }
                     wave_lds_sync();   // staging read before the next plane rewrites it
                     continue;
@@ -963,36 +924,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP ?
                         continue;
                     }
 #endif
-#ifndef LSR_DEFORM_ABL_NOSCATTER   // timing ablation only (wrong plane gradients)
-#ifdef LSR_DEFORM_ABL_NOTIME        // timing ablation only: the time planes' (xt, yt, zt) atomics skipped
-                    if (ci == 2 || ci >= 4) continue;
-#endif
                     if (val != 0.0f) atomicAdd(gp + s_soff[(wave * 16 + j) * 4 + tap] + ch, val);
-#endif
                 }
                 wave_lds_sync();   // staging read before the next plane rewrites it
             }
         };
-#ifndef LSR_DEFORM_HEX_INTERLEAVED
-        {
-            // every scale's taps loaded (and its coordinate gradient formed) before the first scatter:
-            // vmcnt retires in order and counts the atomics, so tap loads issued behind a scale's
-            // atomics waited for them; the scales' dv (24 registers each) stay live in between
-            float4 dvo[S][6];
+        // every scale's taps loaded (and its coordinate gradient formed) before the first scatter:
+        // vmcnt retires in order and counts the atomics, so tap loads issued behind a scale's
+        // atomics waited for them; the scales' dv (24 registers each) stay live in between
+        float4 dvo[S][6];
 #pragma unroll
-            for (int s = 0; s < S; ++s) grad_scale(s, dvo[s]);
-            DSTAMP(12);        // taps, dv and the coordinate gradient of every scale
+        for (int s = 0; s < S; ++s) grad_scale(s, dvo[s]);
+        DSTAMP(12);        // taps, dv and the coordinate gradient of every scale
 #pragma unroll
-            for (int s = 0; s < S; ++s) scatter_scale(s, dvo[s]);
-        }
-#else
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            float4 dvo[6];
-            grad_scale(s, dvo);
-            scatter_scale(s, dvo);
-        }
-#endif
+        for (int s = 0; s < S; ++s) scatter_scale(s, dvo[s]);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             dq[c] += __shfl_xor(dq[c], 1);
@@ -1038,13 +983,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEEP ?
 }
 
 template <int S>
-#ifndef LSR_DEFORM_BWD_DYN_LDS
-#define LSR_DEFORM_BWD_DYN_LDS 0   // diagnostic builds: unused dynamic LDS per block (occupancy control)
-#endif
 static void go_bwd(const DeformBwdArgs& b, hipStream_t st) {
-    const unsigned dyn = LSR_DEFORM_BWD_DYN_LDS;
-    if (b.f.nlayers > 1) hipLaunchKernelGGL((k_deform_bwd_a<S, true>), dim3((b.f.P + DN - 1) / DN), dim3(256), dyn, st, b);
-    else hipLaunchKernelGGL((k_deform_bwd_a<S, false>), dim3((b.f.P + DN - 1) / DN), dim3(256), dyn, st, b);
+    if (b.f.nlayers > 1) hipLaunchKernelGGL((k_deform_bwd_a<S, true>), dim3((b.f.P + DN - 1) / DN), dim3(256), 0, st, b);
+    else hipLaunchKernelGGL((k_deform_bwd_a<S, false>), dim3((b.f.P + DN - 1) / DN), dim3(256), 0, st, b);
 }
 void launch_deform_bwd_a(const DeformBwdArgs& b, hipStream_t st) {
     if (b.f.P <= 0) return;
@@ -1239,11 +1180,11 @@ void launch_lang_deform_bwd(const LangDeformArgs& a, hipStream_t st) {
 }
 
 // ==== head weight gradients by recompute ===========================================================
-// Round 3 saved every head's relu(Z1) and dZ1 rows in phase A (2 x 128 floats per Gaussian per head:
-// 10 GB written and read back at 2M Gaussians with five heads) for the split-K products of k_atb.
-// Here a block walks its rows in tiles of 64 and recomputes them from the saved trunk activation A
-// (512 B per row) and the head's output gradient G:
-//   Z1 = A W1^T + b1 (mlp_ntile, as the forward),  dZ1 = (G W2) * [Z1 > 0] (as phase A),
+// Phase A saves no per-head rows (relu(Z1) and dZ1 would be 2 x 128 floats per Gaussian per head:
+// 10 GB written and read back at 2M Gaussians with five heads).  A block of k_head_wgrad2 (the wide
+// head) or k_head_wgrad3 (the small heads) walks its rows in tiles of 64 and recomputes them from the
+// saved trunk activation A (512 B per row) and the head's output gradient G:
+//   Z1 = A W1^T + b1 (as the forward),  dZ1 = (G W2) * [Z1 > 0] (as phase A),
 //   dW1 += dZ1^T A,  dW2 += G^T relu(Z1),  db1 += sum dZ1,  db2 += sum G,
 // accumulating the block's partial products in registers over all its tiles; one atomic per output
 // element at the end.  The reduction index of the last two products is the row: wave w holds
@@ -1280,213 +1221,21 @@ __device__ __forceinline__ dbf16x8 wg_lds_op(const __bf16* base, int pitch, int 
     return __builtin_bit_cast(dbf16x8, v);
 }
 
-// A rows of a 64-row tile into LDS as bf16 hi / lo (4 values per 8-byte store); rows past row1 are zero
-__device__ __forceinline__ void a_rows_to_lds(const float* __restrict__ A, int64_t t0, int64_t row1, __bf16* ah, __bf16* al) {
-    typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int i = tid; i < DN * (DWID / 4); i += 256) {
-        const int rr = i >> 5, c4 = (i & 31) * 4;
-        const int64_t g = t0 + rr;
-        const float4 v = g < row1 ? *reinterpret_cast<const float4*>(A + g * DWID + c4) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        const float f[4] = {v.x, v.y, v.z, v.w};
-        bf4 h4, l4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            __bf16 hi, lo;
-            dsplit(f[e], hi, lo);
-            h4[e] = hi; l4[e] = lo;
-        }
-        *reinterpret_cast<bf4*>(ah + rr * DAP + c4) = h4;
-        *reinterpret_cast<bf4*>(al + rr * DAP + c4) = l4;
-    }
-}
-
-template <bool SMALL>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) k_head_wgrad(HeadWgradArgs ha, int job0) {
-    __shared__ __attribute__((aligned(16))) __bf16 s_ah[DN * DAP];   // A rows [64][128] hi / lo
-    __shared__ __attribute__((aligned(16))) __bf16 s_al[DN * DAP];
-    __shared__ __attribute__((aligned(16))) __bf16 s_gh[SMALL ? 8 : DN * DGP];   // G rows [64][64 pad] hi / lo
-    __shared__ __attribute__((aligned(16))) __bf16 s_gl[SMALL ? 8 : DN * DGP];
-    __shared__ __attribute__((aligned(16))) float4 s_g4[SMALL ? DN : 1];        // SMALL: G rows fp32
-    LDS_POISON(s_ah); LDS_POISON(s_al); LDS_POISON(s_gh); LDS_POISON(s_gl); LDS_POISON(s_g4); LDS_POISON_DONE();
-    const HeadWgradJob& j = ha.job[job0 + blockIdx.y];
-    const int64_t row0 = (int64_t)blockIdx.x * ha.rows_per_block;
-    const int64_t row1 = min((int64_t)ha.P, row0 + ha.rows_per_block);
-    if (row0 >= row1) return;                                            // block-uniform
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, hh = lane >> 5;
-    const int nout = j.nout, Mo = (nout + 31) / 32;                      // G^T M tiles (1 or 2)
-    const int col = 32 * wave + r;
-    const float b1c = j.b1[col];
-    df32x16 w1acc[4] = {df32x16{}, df32x16{}, df32x16{}, df32x16{}};   // dW1 rows 32 wave .., col tiles 0..3
-    df32x16 w2acc[SMALL ? 1 : 2];                                         // dW2 o tiles 0..1, col tile wave
-    float w2s[DEF_SMALL_OUT] = {0.0f, 0.0f, 0.0f, 0.0f};                 // SMALL: dW2 rows 0..3, column col
-    float w2c[DEF_SMALL_OUT] = {0.0f, 0.0f, 0.0f, 0.0f};                 // SMALL: W2 rows 0..3, column col
-    float4 db2v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if constexpr (SMALL) w2_column(j.w2_h, j.w2_l, col, w2c);
-    else { w2acc[0] = df32x16{}; w2acc[1] = df32x16{}; }
-    float db1 = 0.0f, db2 = 0.0f;
-    for (int64_t t0 = row0; t0 < row1; t0 += DN) {
-        // ---- A and G rows of the tile into LDS; rows past P are zero ------------------------------------
-        a_rows_to_lds(ha.A, t0, row1, s_ah, s_al);
-        if constexpr (SMALL) {
-            if (tid < DN) {   // one row per thread: db2 accumulates in its float4
-                const int64_t g = t0 + tid;
-                float v[DEF_SMALL_OUT] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int k = 0; k < DEF_SMALL_OUT; ++k)
-                    if (k < nout && g < row1) v[k] = j.G[g * nout + k];
-                const float4 gv = make_float4(v[0], v[1], v[2], v[3]);
-                s_g4[tid] = gv;
-                db2v.x += gv.x; db2v.y += gv.y; db2v.z += gv.z; db2v.w += gv.w;
-            }
-        } else {
-            // G rows; a thread always holds column k = tid & 63 (256 is a multiple of 64), so db2, the
-            // column sums of G, accumulate in its register (a per-tile loop of 64 dependent loads by
-            // the nout threads serialised the whole block)
-#pragma unroll
-            for (int i = tid; i < DN * 64; i += 256) {
-                const int rr = i >> 6, k = i & 63;
-                const int64_t g = t0 + rr;
-                const float v = (k < nout && g < row1) ? j.G[g * nout + k] : 0.0f;
-                db2 += v;
-                __bf16 hi, lo;
-                dsplit(v, hi, lo);
-                s_gh[rr * DGP + k] = hi;
-                s_gl[rr * DGP + k] = lo;
-            }
-        }
-        __syncthreads();
-        // ---- Z1 for this wave's 32 columns (both row tiles), then dW2 and dZ1 ------------------------------
-        uint32_t zpos = 0;   // bit 16 mt + q: Z1 > 0
-        df32x16 d[2] = {df32x16{}, df32x16{}};
-        {
-            df32x16 z[2] = {df32x16{}, df32x16{}};
-            mlp_ntile<DWID>(z, s_ah, s_al, DAP, wave, j.w1_h, j.w1_l);
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const float zz = z[mt][q] + b1c;
-                    zpos |= zz > 0.0f ? 1u << (16 * mt + q) : 0u;
-                    z[mt][q] = fmaxf(zz, 0.0f);
-                }
-            if constexpr (SMALL) {
-                // per row of the lane: dW2[k][col] += G[r][k] relu(Z1)[r][col], dZ1 = sum_k G[r][k] W2[k][col]
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) {
-                        const float4 gv = s_g4[row_of(mt, q, hh)];
-                        const float zz = z[mt][q];
-                        w2s[0] = __builtin_fmaf(gv.x, zz, w2s[0]); w2s[1] = __builtin_fmaf(gv.y, zz, w2s[1]);
-                        w2s[2] = __builtin_fmaf(gv.z, zz, w2s[2]); w2s[3] = __builtin_fmaf(gv.w, zz, w2s[3]);
-                        float dv = gv.x * w2c[0];
-                        dv = __builtin_fmaf(gv.y, w2c[1], dv);
-                        dv = __builtin_fmaf(gv.z, w2c[2], dv);
-                        dv = __builtin_fmaf(gv.w, w2c[3], dv);
-                        d[mt][q] = dv;
-                    }
-            } else {
-#pragma unroll
-                for (int ks = 0; ks < DN / 16; ++ks) {
-                    dbf16x8 zh, zl;
-                    wg_regs_to_op(z[ks >> 1], ks & 1, zh, zl);
-#pragma unroll
-                    for (int mo = 0; mo < 2; ++mo) {
-                        if (mo >= Mo) break;
-                        const dbf16x8 gh = wg_lds_op(s_gh, DGP, ks, 32 * mo), gl = wg_lds_op(s_gl, DGP, ks, 32 * mo);
-                        w2acc[mo] = DMFMA(gh, zh, w2acc[mo]);
-                        w2acc[mo] = DMFMA(gh, zl, w2acc[mo]);
-                        w2acc[mo] = DMFMA(gl, zh, w2acc[mo]);
-                    }
-                }
-            }
-        }
-        // ---- dZ1 = (G W2) [Z1 > 0] -> dW1 += dZ1^T A (rows 32 wave .. of dW1), db1 ------------------------
-        {
-            if constexpr (!SMALL) mlp_ntile<64>(d, s_gh, s_gl, DGP, wave, j.w2t_h, j.w2t_l);
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    d[mt][q] = (zpos >> (16 * mt + q)) & 1u ? d[mt][q] : 0.0f;
-                    db1 += d[mt][q];
-                }
-#pragma unroll
-            for (int ks = 0; ks < DN / 16; ++ks) {
-                dbf16x8 dh, dl;
-                wg_regs_to_op(d[ks >> 1], ks & 1, dh, dl);
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) {
-                    const dbf16x8 bh = wg_lds_op(s_ah, DAP, ks, 32 * nt), bl = wg_lds_op(s_al, DAP, ks, 32 * nt);
-                    w1acc[nt] = DMFMA(dh, bh, w1acc[nt]);
-                    w1acc[nt] = DMFMA(dh, bl, w1acc[nt]);
-                    w1acc[nt] = DMFMA(dl, bh, w1acc[nt]);
-                }
-            }
-        }
-        __syncthreads();   // the tile's LDS rows read before the next tile overwrites them
-    }
-    // ---- the block's partial products: one atomic per element ------------------------------------------
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int m = 32 * wave + (q & 3) + 8 * (q >> 2) + 4 * hh;
-            atomicAdd(j.dW1 + (size_t)m * DWID + 32 * nt + r, w1acc[nt][q]);
-        }
-    db1 += __shfl_xor(db1, 32);
-    if (hh == 0) atomicAdd(j.db1 + col, db1);
-    if constexpr (SMALL) {
-#pragma unroll
-        for (int k = 0; k < DEF_SMALL_OUT; ++k) {
-            const float v = w2s[k] + __shfl_xor(w2s[k], 32);   // the lane pair holds the column's two row halves
-            if (hh == 0 && k < nout) atomicAdd(j.dW2 + (size_t)k * DWID + col, v);
-        }
-        if (wave == 0) {   // db2: the 64 row threads' sums
-            float v[DEF_SMALL_OUT] = {db2v.x, db2v.y, db2v.z, db2v.w};
-#pragma unroll
-            for (int k = 0; k < DEF_SMALL_OUT; ++k) {
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_xor(v[k], off);
-                if (lane == 0 && k < nout) atomicAdd(j.db2 + k, v[k]);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int mo = 0; mo < 2; ++mo) {
-            if (mo >= Mo) break;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int o = 32 * mo + (q & 3) + 8 * (q >> 2) + 4 * hh;
-                if (o < nout) atomicAdd(j.dW2 + (size_t)o * DWID + col, w2acc[mo][q]);
-            }
-        }
-        if ((tid & 63) < nout) atomicAdd(j.db2 + (tid & 63), db2);   // one partial per wave
-    }
-}
-
-// Version 2 (round 6): the same products at ONE wave per SIMD, with what version 1 re-read per 64-row
-// tile held in registers for the whole block -- the wave's W1 fragments (its 32 columns, K = 128: 64
-// registers) and, for the wide heads, its W2^T fragments (K = 64: 32 registers) -- and the next tile's
-// A and G rows loaded into registers while the current tile computes (version 1 waited on an L2 round
-// trip of 64 KB of weight fragments and one of the tile's rows per tile, at 2 waves per SIMD with no
-// registers left to prefetch).  The accumulators move to AGPRs (512 registers per wave at one wave
-// per SIMD).  Blocks: 64 per small head (the four share each row range on one XCD: grid x is a
-// multiple of 8, so their A reads meet in that XCD's L2) and 256 for a wide head, one round of 256
-// CUs each.
-template <bool SMALL>
+// The wide head (SH: more than DEF_SMALL_OUT outputs, every product on the matrix core), at ONE wave
+// per SIMD: 512 registers per wave, the accumulators in AGPRs.  What every 64-row tile needs stays
+// on the CU for the whole block -- the wave's W1 fragments in registers (its 32 columns, K = 128: 64
+// registers) and W2^T in LDS (registers would spill) -- and the next tile's A and G rows are loaded
+// into registers while the current tile computes, so a tile waits neither on an L2 round trip of
+// weight fragments nor on its own rows.  256 blocks per wide head: one round of the 256 CUs.
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) k_head_wgrad2(HeadWgradArgs ha, int job0) {
     __shared__ __attribute__((aligned(16))) __bf16 s_ah[DN * DAP];   // A rows [64][128] hi / lo
     __shared__ __attribute__((aligned(16))) __bf16 s_al[DN * DAP];
-    __shared__ __attribute__((aligned(16))) __bf16 s_gh[SMALL ? 8 : DN * DGP];   // G rows [64][64 pad] hi / lo
-    __shared__ __attribute__((aligned(16))) __bf16 s_gl[SMALL ? 8 : DN * DGP];
-    __shared__ __attribute__((aligned(16))) float4 s_g4[SMALL ? DN : 1];        // SMALL: G rows fp32
-    __shared__ __attribute__((aligned(16))) __bf16 s_w2h[SMALL ? 8 : DWID * DLP];   // !SMALL: W2^T [128][64 pad]
-    __shared__ __attribute__((aligned(16))) __bf16 s_w2l[SMALL ? 8 : DWID * DLP];
-    LDS_POISON(s_ah); LDS_POISON(s_al); LDS_POISON(s_gh); LDS_POISON(s_gl); LDS_POISON(s_g4); LDS_POISON(s_w2h);
-    LDS_POISON(s_w2l); LDS_POISON_DONE();
+    __shared__ __attribute__((aligned(16))) __bf16 s_gh[DN * DGP];   // G rows [64][64 pad] hi / lo
+    __shared__ __attribute__((aligned(16))) __bf16 s_gl[DN * DGP];
+    __shared__ __attribute__((aligned(16))) __bf16 s_w2h[DWID * DLP];   // W2^T [128][64 pad]
+    __shared__ __attribute__((aligned(16))) __bf16 s_w2l[DWID * DLP];
+    LDS_POISON(s_ah); LDS_POISON(s_al); LDS_POISON(s_gh); LDS_POISON(s_gl); LDS_POISON(s_w2h); LDS_POISON(s_w2l);
+    LDS_POISON_DONE();
     typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
     const HeadWgradJob& j = ha.job[job0 + blockIdx.y];
     const int64_t row0 = (int64_t)blockIdx.x * ha.rows_per_block;
@@ -1504,24 +1253,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         w1h[ks] = *reinterpret_cast<const dbf16x8*>(j.w1_h + wo);
         w1l[ks] = *reinterpret_cast<const dbf16x8*>(j.w1_l + wo);
     }
-    if constexpr (!SMALL) {   // the wide head's W2^T in LDS (registers would spill), visible after the first barrier
-        for (int i = tid; i < DWID * 64 / 8; i += 256) {
-            const int rr = i >> 3, c8 = (i & 7) * 8;
-            *reinterpret_cast<dbf16x8*>(s_w2h + rr * DLP + c8) = *reinterpret_cast<const dbf16x8*>(j.w2t_h + rr * 64 + c8);
-            *reinterpret_cast<dbf16x8*>(s_w2l + rr * DLP + c8) = *reinterpret_cast<const dbf16x8*>(j.w2t_l + rr * 64 + c8);
-        }
+    for (int i = tid; i < DWID * 64 / 8; i += 256) {   // W2^T into LDS, visible after the first barrier
+        const int rr = i >> 3, c8 = (i & 7) * 8;
+        *reinterpret_cast<dbf16x8*>(s_w2h + rr * DLP + c8) = *reinterpret_cast<const dbf16x8*>(j.w2t_h + rr * 64 + c8);
+        *reinterpret_cast<dbf16x8*>(s_w2l + rr * DLP + c8) = *reinterpret_cast<const dbf16x8*>(j.w2t_l + rr * 64 + c8);
     }
     df32x16 w1acc[4] = {df32x16{}, df32x16{}, df32x16{}, df32x16{}};   // dW1 rows 32 wave .., col tiles 0..3
-    df32x16 w2acc[SMALL ? 1 : 2];                                         // dW2 o tiles 0..1, col tile wave
-    float w2s[DEF_SMALL_OUT] = {0.0f, 0.0f, 0.0f, 0.0f};                 // SMALL: dW2 rows 0..3, column col
-    float w2c[DEF_SMALL_OUT] = {0.0f, 0.0f, 0.0f, 0.0f};                 // SMALL: W2 rows 0..3, column col
-    float4 db2v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if constexpr (SMALL) w2_column(j.w2_h, j.w2_l, col, w2c);
-    else { w2acc[0] = df32x16{}; w2acc[1] = df32x16{}; }
+    df32x16 w2acc[2] = {df32x16{}, df32x16{}};                           // dW2 o tiles 0..1, col tile wave
     float db1 = 0.0f, db2 = 0.0f;
     // ---- the tile's rows in registers: A (thread: 8 float4 of rows (tid + 256 i) >> 5), G ---------------
     float4 pa[DN * DWID / 4 / 256];
-    float pg[SMALL ? DEF_SMALL_OUT : DN * 64 / 256];
+    float pg[DN * 64 / 256];
     auto load_tile = [&](int64_t t0) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < DN * DWID / 4 / 256; ++i) {
@@ -1529,17 +1271,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             const int64_t g = t0 + rr;
             pa[i] = g < row1 ? *reinterpret_cast<const float4*>(ha.A + g * DWID + c4) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
-        if constexpr (SMALL) {
-            const int64_t g = t0 + tid;
 #pragma unroll
-            for (int k = 0; k < DEF_SMALL_OUT; ++k) pg[k] = (tid < DN && k < nout && g < row1) ? j.G[g * nout + k] : 0.0f;
-        } else {
-#pragma unroll
-            for (int i = 0; i < DN * 64 / 256; ++i) {
-                const int e = tid + 256 * i, rr = e >> 6, k = e & 63;
-                const int64_t g = t0 + rr;
-                pg[i] = (k < nout && g < row1) ? j.G[g * nout + k] : 0.0f;
-            }
+        for (int i = 0; i < DN * 64 / 256; ++i) {
+            const int e = tid + 256 * i, rr = e >> 6, k = e & 63;
+            const int64_t g = t0 + rr;
+            pg[i] = (k < nout && g < row1) ? j.G[g * nout + k] : 0.0f;
         }
     };
     auto store_tile = [&]() __attribute__((always_inline)) {
@@ -1557,22 +1293,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             *reinterpret_cast<bf4*>(s_ah + rr * DAP + c4) = h4;
             *reinterpret_cast<bf4*>(s_al + rr * DAP + c4) = l4;
         }
-        if constexpr (SMALL) {
-            if (tid < DN) {
-                const float4 gv = make_float4(pg[0], pg[1], pg[2], pg[3]);
-                s_g4[tid] = gv;
-                db2v.x += gv.x; db2v.y += gv.y; db2v.z += gv.z; db2v.w += gv.w;
-            }
-        } else {
 #pragma unroll
-            for (int i = 0; i < DN * 64 / 256; ++i) {   // column k = tid & 63 for every i: db2 in a register
-                const int e = tid + 256 * i, rr = e >> 6, k = e & 63;
-                db2 += pg[i];
-                __bf16 hi, lo;
-                dsplit(pg[i], hi, lo);
-                s_gh[rr * DGP + k] = hi;
-                s_gl[rr * DGP + k] = lo;
-            }
+        for (int i = 0; i < DN * 64 / 256; ++i) {   // column k = tid & 63 for every i: db2 in a register
+            const int e = tid + 256 * i, rr = e >> 6, k = e & 63;
+            db2 += pg[i];
+            __bf16 hi, lo;
+            dsplit(pg[i], hi, lo);
+            s_gh[rr * DGP + k] = hi;
+            s_gl[rr * DGP + k] = lo;
         }
     };
     load_tile(row0);
@@ -1605,53 +1333,34 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
                     zpos |= zz > 0.0f ? 1u << (16 * mt + q) : 0u;
                     z[mt][q] = fmaxf(zz, 0.0f);
                 }
-            if constexpr (SMALL) {
 #pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
+            for (int ks = 0; ks < DN / 16; ++ks) {
+                dbf16x8 zh, zl;
+                wg_regs_to_op(z[ks >> 1], ks & 1, zh, zl);
 #pragma unroll
-                    for (int q = 0; q < 16; ++q) {
-                        const float4 gv = s_g4[row_of(mt, q, hh)];
-                        const float zz = z[mt][q];
-                        w2s[0] = __builtin_fmaf(gv.x, zz, w2s[0]); w2s[1] = __builtin_fmaf(gv.y, zz, w2s[1]);
-                        w2s[2] = __builtin_fmaf(gv.z, zz, w2s[2]); w2s[3] = __builtin_fmaf(gv.w, zz, w2s[3]);
-                        float dv = gv.x * w2c[0];
-                        dv = __builtin_fmaf(gv.y, w2c[1], dv);
-                        dv = __builtin_fmaf(gv.z, w2c[2], dv);
-                        dv = __builtin_fmaf(gv.w, w2c[3], dv);
-                        d[mt][q] = dv;
-                    }
-            } else {
-#pragma unroll
-                for (int ks = 0; ks < DN / 16; ++ks) {
-                    dbf16x8 zh, zl;
-                    wg_regs_to_op(z[ks >> 1], ks & 1, zh, zl);
-#pragma unroll
-                    for (int mo = 0; mo < 2; ++mo) {
-                        if (mo >= Mo) break;
-                        const dbf16x8 gh = wg_lds_op(s_gh, DGP, ks, 32 * mo), gl = wg_lds_op(s_gl, DGP, ks, 32 * mo);
-                        w2acc[mo] = DMFMA(gh, zh, w2acc[mo]);
-                        w2acc[mo] = DMFMA(gh, zl, w2acc[mo]);
-                        w2acc[mo] = DMFMA(gl, zh, w2acc[mo]);
-                    }
+                for (int mo = 0; mo < 2; ++mo) {
+                    if (mo >= Mo) break;
+                    const dbf16x8 gh = wg_lds_op(s_gh, DGP, ks, 32 * mo), gl = wg_lds_op(s_gl, DGP, ks, 32 * mo);
+                    w2acc[mo] = DMFMA(gh, zh, w2acc[mo]);
+                    w2acc[mo] = DMFMA(gh, zl, w2acc[mo]);
+                    w2acc[mo] = DMFMA(gl, zh, w2acc[mo]);
                 }
             }
         }
         // ---- dZ1 = (G W2) [Z1 > 0] -> dW1 += dZ1^T A (rows 32 wave .. of dW1), db1 ------------------------
         {
-            if constexpr (!SMALL) {
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const int k0 = 16 * ks + 8 * hh;
-                    const dbf16x8 w2h = *reinterpret_cast<const dbf16x8*>(s_w2h + col * DLP + k0);
-                    const dbf16x8 w2l = *reinterpret_cast<const dbf16x8*>(s_w2l + col * DLP + k0);
+            for (int ks = 0; ks < 4; ++ks) {
+                const int k0 = 16 * ks + 8 * hh;
+                const dbf16x8 w2h = *reinterpret_cast<const dbf16x8*>(s_w2h + col * DLP + k0);
+                const dbf16x8 w2l = *reinterpret_cast<const dbf16x8*>(s_w2l + col * DLP + k0);
 #pragma unroll
-                    for (int mt = 0; mt < 2; ++mt) {
-                        const dbf16x8 gh = *reinterpret_cast<const dbf16x8*>(s_gh + (32 * mt + r) * DGP + k0);
-                        const dbf16x8 gl = *reinterpret_cast<const dbf16x8*>(s_gl + (32 * mt + r) * DGP + k0);
-                        d[mt] = DMFMA(gh, w2h, d[mt]);
-                        d[mt] = DMFMA(gh, w2l, d[mt]);
-                        d[mt] = DMFMA(gl, w2h, d[mt]);
-                    }
+                for (int mt = 0; mt < 2; ++mt) {
+                    const dbf16x8 gh = *reinterpret_cast<const dbf16x8*>(s_gh + (32 * mt + r) * DGP + k0);
+                    const dbf16x8 gl = *reinterpret_cast<const dbf16x8*>(s_gl + (32 * mt + r) * DGP + k0);
+                    d[mt] = DMFMA(gh, w2h, d[mt]);
+                    d[mt] = DMFMA(gh, w2l, d[mt]);
+                    d[mt] = DMFMA(gl, w2h, d[mt]);
                 }
             }
 #pragma unroll
@@ -1676,7 +1385,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         }
         __syncthreads();   // the tile's LDS rows read before the next tile's are stored
     }
-    // ---- the block's partial products: one atomic per element (as version 1) ---------------------------
+    // ---- the block's partial products: one atomic per element ------------------------------------------
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
@@ -1686,49 +1395,34 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         }
     db1 += __shfl_xor(db1, 32);
     if (hh == 0) atomicAdd(j.db1 + col, db1);
-    if constexpr (SMALL) {
 #pragma unroll
-        for (int k = 0; k < DEF_SMALL_OUT; ++k) {
-            const float v = w2s[k] + __shfl_xor(w2s[k], 32);
-            if (hh == 0 && k < nout) atomicAdd(j.dW2 + (size_t)k * DWID + col, v);
+    for (int mo = 0; mo < 2; ++mo) {
+        if (mo >= Mo) break;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int o = 32 * mo + (q & 3) + 8 * (q >> 2) + 4 * hh;
+            if (o < nout) atomicAdd(j.dW2 + (size_t)o * DWID + col, w2acc[mo][q]);
         }
-        if (wave == 0) {
-            float v[DEF_SMALL_OUT] = {db2v.x, db2v.y, db2v.z, db2v.w};
-#pragma unroll
-            for (int k = 0; k < DEF_SMALL_OUT; ++k) {
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_xor(v[k], off);
-                if (lane == 0 && k < nout) atomicAdd(j.db2 + k, v[k]);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int mo = 0; mo < 2; ++mo) {
-            if (mo >= Mo) break;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int o = 32 * mo + (q & 3) + 8 * (q >> 2) + 4 * hh;
-                if (o < nout) atomicAdd(j.dW2 + (size_t)o * DWID + col, w2acc[mo][q]);
-            }
-        }
-        if ((tid & 63) < nout) atomicAdd(j.db2 + (tid & 63), db2);
     }
+    if ((tid & 63) < nout) atomicAdd(j.db2 + (tid & 63), db2);   // one partial per wave
 }
 
-// Version 3 (round 6, the small heads): version 2's products software-pipelined across tiles so that
-// one wave per SIMD keeps its matrix core fed.  Three LDS tile buffers; iteration t runs
+// The small heads (at most DEF_SMALL_OUT outputs: G W2 and G^T relu(Z1) on the VALU from fp32 G rows,
+// Z1 and dW1 on the matrix core), software-pipelined across tiles so that one wave per SIMD keeps its
+// matrix core fed.  The wave's W1 hi fragments stay in registers for the whole block and the
+// accumulators in AGPRs.  Three LDS tile buffers; iteration t runs
 //   A: Z1 of tile t + 1 (MFMA, buffer t + 1)  beside  relu / dZ1 / dW2 of tile t (VALU, Z1(t) in registers)
 //   B: dW1 += dZ1(t)^T A(t) (MFMA, buffer t)   beside  tile t + 2's rows into buffer t + 2 (VALU + LDS stores)
 // then tile t + 3's rows are loaded into registers and one barrier ends the iteration (buffer t is
 // free for tile t + 3, tile t + 2 is visible).  An iteration is branch-free (loads at clamped rows,
 // zeros selected past the block's rows; Z1 past the last tile is computed and dropped) and each stage
 // interleaves its two chains by hand, K step by K step, fenced by sched_barrier (sched_group_barrier
-// patterns did not take: the compiler hoisted the VALU chain out of the MFMA region).  Version 2 ran
-// the chains one after the other: 2.27 -> 2.03 ms for the four small heads at 2M.  W1's lo half sits
-// in LDS (registers hold the hi half) so that nothing spills.
-template <bool SMALL>
+// patterns did not take: the compiler hoisted the VALU chain out of the MFMA region).  With the two
+// chains run one after the other, tile by tile, the four small heads took 2.27 ms at 2M; interleaved
+// 2.03 ms.  W1's lo half sits in LDS (registers hold the hi half) so that nothing spills.  64 blocks
+// per small head: the four share each row range on one XCD (grid x is a multiple of 8), so their A
+// reads meet in that XCD's L2, and the launch is one round of the 256 CUs.
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) k_head_wgrad3(HeadWgradArgs ha, int job0) {
-    static_assert(SMALL, "version 3 covers the heads of at most DEF_SMALL_OUT outputs");
     constexpr int NB = 3;
     __shared__ __attribute__((aligned(16))) __bf16 s_ah[NB][DN * DAP];   // A rows [64][128] hi / lo
     __shared__ __attribute__((aligned(16))) __bf16 s_al[NB][DN * DAP];
@@ -1905,7 +1599,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         __syncthreads();
         zc[0] = zn[0]; zc[1] = zn[1];
     }
-    // ---- the block's partial products: one atomic per element (as version 1) ---------------------------
+    // ---- the block's partial products: one atomic per element ------------------------------------------
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
@@ -1931,17 +1625,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     }
 }
 
-// Rows per block of a launch, for about `blocks` blocks per head: 128 for the small-output heads
-// (their per-block flush of dW1 / dW2 partials is most of their atomics), 400 for the SH head.
-// Measured against the split-K default of 256 blocks per head: deformation backward 11.96-11.99
-// -> 11.20-11.21 ms at 2M, configs[4] stand-in 1.449-1.454 -> 1.391-1.400 ms per iteration.
-// LSR_WGRAD_ROWS_SMALL / LSR_WGRAD_ROWS_BIG override (diagnostic A/B).
-static int wgrad_rows(const char* env, int P, int blocks) {
-    const char* e = std::getenv(env);
-    const int r = e ? std::atoi(e) : 0;
-    if (r >= 64) return r / 64 * 64;
-    return std::max(64, ((P + blocks - 1) / blocks + 63) / 64 * 64);
-}
 void launch_head_wgrad(const HeadWgradArgs& a, int njobs, hipStream_t st) {
     if (a.P <= 0 || njobs <= 0) return;
     // the small-output heads first (one launch), then the rest: jobs are reordered into two runs
@@ -1951,34 +1634,19 @@ void launch_head_wgrad(const HeadWgradArgs& a, int njobs, hipStream_t st) {
         if (a.job[i].nout <= DEF_SMALL_OUT) s.job[ns++] = a.job[i];
     for (int i = 0; i < njobs; ++i)
         if (a.job[i].nout > DEF_SMALL_OUT) { s.job[ns + nbig] = a.job[i]; ++nbig; }
-    // version 3 for the small heads, 2 for the wide by default (2M backward 10.10 -> 9.34 (v2) -> 9.13-9.15 ms);
-    // LSR_WGRAD_V=1 / 2: the earlier versions (diagnostic A/B)
-    static const int ver = [] { const char* e = std::getenv("LSR_WGRAD_V"); return e ? std::atoi(e) : 3; }();
-    if (ver >= 2) {   // one round of 256 CUs per launch: 64 blocks per small head, 256 for a wide head
-        if (ns) {
-            const int nb = ns <= 4 ? 256 / ns / 8 * 8 : 32;
-            s.rows_per_block = std::max(64, ((a.P + nb - 1) / nb + 63) / 64 * 64);
-            const dim3 grid((a.P + s.rows_per_block - 1) / s.rows_per_block, ns);
-            if (ver == 3) hipLaunchKernelGGL(k_head_wgrad3<true>, grid, dim3(256), 0, st, s, 0);
-            else hipLaunchKernelGGL(k_head_wgrad2<true>, grid, dim3(256), 0, st, s, 0);
-        }
-        if (nbig) {
-            const int nb = std::max(8, 256 / nbig / 8 * 8);
-            s.rows_per_block = std::max(64, ((a.P + nb - 1) / nb + 63) / 64 * 64);
-            hipLaunchKernelGGL(k_head_wgrad2<false>, dim3((a.P + s.rows_per_block - 1) / s.rows_per_block, nbig),
-                               dim3(256), 0, st, s, ns);
-        }
-        return;
-    }
+    // one round of 256 CUs per launch: 64 blocks per small head, 256 for a wide head (2M backward
+    // 9.34 ms with the small heads unpipelined -> 9.13-9.15 ms)
     if (ns) {
-        s.rows_per_block = wgrad_rows("LSR_WGRAD_ROWS_SMALL", a.P, 128);
-        const int nb = (a.P + s.rows_per_block - 1) / s.rows_per_block;
-        hipLaunchKernelGGL(k_head_wgrad<true>, dim3(nb, ns), dim3(256), 0, st, s, 0);
+        const int nb = ns <= 4 ? 256 / ns / 8 * 8 : 32;
+        s.rows_per_block = std::max(64, ((a.P + nb - 1) / nb + 63) / 64 * 64);
+        hipLaunchKernelGGL(k_head_wgrad3, dim3((a.P + s.rows_per_block - 1) / s.rows_per_block, ns), dim3(256), 0, st,
+                           s, 0);
     }
     if (nbig) {
-        s.rows_per_block = wgrad_rows("LSR_WGRAD_ROWS_BIG", a.P, 400);
-        const int nb = (a.P + s.rows_per_block - 1) / s.rows_per_block;
-        hipLaunchKernelGGL(k_head_wgrad<false>, dim3(nb, nbig), dim3(256), 0, st, s, ns);
+        const int nb = std::max(8, 256 / nbig / 8 * 8);
+        s.rows_per_block = std::max(64, ((a.P + nb - 1) / nb + 63) / 64 * 64);
+        hipLaunchKernelGGL(k_head_wgrad2, dim3((a.P + s.rows_per_block - 1) / s.rows_per_block, nbig), dim3(256), 0,
+                           st, s, ns);
     }
 }
 
@@ -2069,13 +1737,8 @@ __global__ void __launch_bounds__(256) k_atb(AtbArgs ga) {
 
 void launch_atb(const AtbArgs& a, int njobs, hipStream_t st) {
     if (a.P <= 0 || njobs <= 0) return;
-    AtbArgs s = a;
-    if (const char* e = std::getenv("LSR_ATB_BLOCKS")) {   // diagnostic A/B: blocks per job
-        const int nbt = std::max(1, std::atoi(e));
-        s.rows_per_block = std::max(64, ((a.P + nbt - 1) / nbt + 63) / 64 * 64);
-    }
-    const int nb = (s.P + s.rows_per_block - 1) / s.rows_per_block;
-    hipLaunchKernelGGL(k_atb, dim3(nb, njobs), dim3(256), 0, st, s);
+    const int nb = (a.P + a.rows_per_block - 1) / a.rows_per_block;
+    hipLaunchKernelGGL(k_atb, dim3(nb, njobs), dim3(256), 0, st, a);
 }
 
 // packed channel-last gradient replicas [r][H][W][16] -> torch [16][H][W], summed over the replicas
@@ -2132,50 +1795,14 @@ void launch_unpack_planes(const UnpackBatch& u, hipStream_t st) {
 }
 
 // ---- parameter packing ----------------------------------------------------------------------------
-// plane [C=16][H][W] (torch) -> [H][W][16]
-__global__ void k_pack_plane(const float* __restrict__ src, float* __restrict__ dst, int H, int W) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;   // over H * W * 16 destination floats
-    if (i >= H * W * 16) return;
-    const int c = i & 15, hw = i >> 4;
-    dst[i] = src[(size_t)c * H * W + hw];
-}
-
-// fp32 [rows][cols] -> bf16 hi / lo [rows_pad][cols_pad], zero past `rows` / `cols`
-__global__ void k_pack_weight(const float* __restrict__ src, __bf16* __restrict__ hi, __bf16* __restrict__ lo,
-                              int rows, int rows_pad, int cols, int cols_pad) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows_pad * cols_pad) return;
-    const int r = i / cols_pad, c = i - r * cols_pad;
-    const float v = (r < rows && c < cols) ? src[(size_t)r * cols + c] : 0.0f;
-    __bf16 h, l;
-    dsplit(v, h, l);
-    hi[i] = h;
-    lo[i] = l;
-}
-
-// fp32 [rows][cols] -> bf16 hi / lo [cols_pad][k_pad], dst[c][r] = src[r][c], zero for r >= rows, c >= cols
-__global__ void k_pack_weight_t(const float* __restrict__ src, __bf16* __restrict__ hi, __bf16* __restrict__ lo,
-                                int rows, int cols, int k_pad, int cols_pad) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= cols_pad * k_pad) return;
-    const int c = i / k_pad, r = i - c * k_pad;
-    const float v = (r < rows && c < cols) ? src[(size_t)r * cols + c] : 0.0f;
-    __bf16 h, l;
-    dsplit(v, h, l);
-    hi[i] = h;
-    lo[i] = l;
-}
-
-void launch_pack_weight_t(const float* src, __bf16* hi, __bf16* lo, int rows, int cols, int k_pad, int cols_pad,
-                          hipStream_t st) {
-    hipLaunchKernelGGL(k_pack_weight_t, dim3((cols_pad * k_pad + 255) / 256), dim3(256), 0, st, src, hi, lo, rows, cols,
-                       k_pad, cols_pad);
-}
-
 // Every packing job of lsr_deform_prepare (planes, weights, transposed weights: ~34 per field) in
 // one launch: block b runs job j where first[j] <= b < first[j + 1] (a scalar search over <= 48
-// jobs); the element work is that of the single-job kernels above.  (One launch per job left the
-// device idle between ~34 tiny kernels every training iteration.)
+// jobs), one thread per destination element i of the job's layout:
+//   plane:             fp32 [16][H][W] (torch) -> fp32 [H][W][16], dst[hw][c] = src[c][hw]
+//   weight:            fp32 [rows][cols] -> bf16 hi / lo [rows_pad][cols_pad], zero past rows / cols
+//   transposed weight: fp32 [rows][cols] -> bf16 hi / lo [cols_pad][k_pad], dst[c][r] = src[r][c],
+//                      zero for r >= rows, c >= cols
+// (One launch per job left the device idle between ~34 tiny kernels every training iteration.)
 __global__ void __launch_bounds__(256) k_pack_batch(PackBatch pb) {
     const uint32_t b = blockIdx.x;
     int j = 0;
@@ -2218,15 +1845,6 @@ void launch_pack_batch(PackJob* jobs, int n, hipStream_t st) {
         }
         if (blocks) hipLaunchKernelGGL(k_pack_batch, dim3(blocks), dim3(256), 0, st, pb);
     }
-}
-
-void launch_pack_plane(const float* src, float* dst, int H, int W, hipStream_t st) {
-    hipLaunchKernelGGL(k_pack_plane, dim3((H * W * 16 + 255) / 256), dim3(256), 0, st, src, dst, H, W);
-}
-void launch_pack_weight(const float* src, __bf16* hi, __bf16* lo, int rows, int rows_pad, int cols, int cols_pad,
-                        hipStream_t st) {
-    hipLaunchKernelGGL(k_pack_weight, dim3((rows_pad * cols_pad + 255) / 256), dim3(256), 0, st, src, hi, lo, rows,
-                       rows_pad, cols, cols_pad);
 }
 
 }  // namespace lsr

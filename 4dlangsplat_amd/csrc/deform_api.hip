@@ -483,7 +483,7 @@ extern "C" int lsr_deform_backward(const lsr_deform_net* net, const void* worksp
     }
     // weight gradients, split-K over row blocks: the feature_out chain and lang_deform as A^T B
     // products of saved rows (k_atb); every computed head by recompute from the trunk's last
-    // activation (k_head_wgrad: no per-head rows saved)
+    // activation (k_head_wgrad2 / k_head_wgrad3: no per-head rows saved)
     lsr::AtbArgs g{};
     g.P = P;
     // ~1024 blocks per job (4 per CU: the per-block row loops are latency-bound; 256 blocks measured

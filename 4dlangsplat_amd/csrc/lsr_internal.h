@@ -263,7 +263,6 @@ struct DeformArgs {
     float* out_coff;                  // DISCRETE: [P, centers] or null
 };
 void launch_deform_fwd(const DeformArgs& a, hipStream_t st);
-void launch_pack_plane(const float* src, float* dst, int H, int W, hipStream_t st);
 // lsr_deform_prepare's packing jobs in one launch per PACK_MAX_JOBS (k_pack_batch)
 enum PackKind { PACK_PLANE = 0, PACK_WEIGHT = 1, PACK_WEIGHT_T = 2 };
 struct PackJob {
@@ -276,12 +275,6 @@ struct PackJob {
 constexpr int PACK_MAX_JOBS = 64;
 struct PackBatch { PackJob j[PACK_MAX_JOBS]; int n; };
 void launch_pack_batch(PackJob* jobs, int n, hipStream_t st);
-void launch_pack_weight(const float* src, __bf16* hi, __bf16* lo, int rows, int rows_pad, int cols, int cols_pad,
-                        hipStream_t st);
-// transposed packing: src fp32 [rows][cols] -> hi / lo [cols_pad][k_pad] with dst[c][r] = src[r][c],
-// zero for r >= rows or c >= cols
-void launch_pack_weight_t(const float* src, __bf16* hi, __bf16* lo, int rows, int cols, int k_pad, int cols_pad,
-                          hipStream_t st);
 
 // deformation backward (deform.hip): phase A per 64 Gaussians (recompute, data gradients, plane
 // scatter, saved activations), phase B the weight gradients as split-K A^T B products
@@ -319,10 +312,11 @@ struct DeformBwdArgs {
 };
 constexpr int DEF_AABB_SLOTS = 64;
 void launch_deform_bwd_a(const DeformBwdArgs& a, hipStream_t st);
-// Weight gradients of the computed heads by recompute (deform.hip k_head_wgrad): per head and block
-// of rows, from the saved last trunk activation A and the head's output gradient G,
-// Z1 = A W1^T + b1, dZ1 = (G W2) [Z1 > 0]; dW1 += dZ1^T A, db1 += sum dZ1, dW2 += G^T relu(Z1),
-// db2 += sum G.  One launch for every head (grid row = job).
+// Weight gradients of the computed heads by recompute (deform.hip: k_head_wgrad3 for the heads of
+// at most 4 outputs, k_head_wgrad2 for the wide SH head): per head and block of rows, from the saved
+// last trunk activation A and the head's output gradient G, Z1 = A W1^T + b1, dZ1 = (G W2) [Z1 > 0];
+// dW1 += dZ1^T A, db1 += sum dZ1, dW2 += G^T relu(Z1), db2 += sum G.  One launch per kernel (grid
+// row = job).
 struct HeadWgradJob {
     const float* G;                   // [P][nout]
     const __bf16 *w1_h, *w1_l;        // forward pack [128][128]

@@ -2,7 +2,8 @@
 // "s_waitcnt vmcnt(0) expcnt(0) lgkmcnt(0)" before nearly every instruction, and the hazard recognizer
 // then counts each of them as one wait state and drops the s_nop it had placed for a hazard.  In the
 // deformation build the dropped nops guard (among others) "VALU writes VCC -> v_cndmask reads VCC" in
-// the unsigned-division fix-up of k_pack_weight, whose quotient is a row index.  This kernel runs that
+// the unsigned-division fix-up of k_pack_batch's weight job, whose quotient i / cols_pad is a row index.
+// This kernel runs that
 // exact instruction pattern on data: 32-bit unsigned division / remainder by a kernel argument (the
 // quotient fix-ups are v_cmp -> v_cndmask pairs) and a correctly rounded sqrt (v_cmp_class -> v_cndmask),
 // and stores the results (no data-dependent addressing, so a wrong value cannot fault).

@@ -79,8 +79,8 @@ def test_waitcnt_forcezero_hazard(tmp_path):
     s_nop wait states) and with the debug flag (whose inserted s_waitcnt the recognizer counts as wait
     states and drops the s_nop).  The library build must be exact; the flag build's count is reported:
     wrong quotients there mean an s_waitcnt with nothing outstanding supplies no wait state, so that
-    flag's code under-pads the hazards (in k_pack_weight the quotient is a row index: an out-of-range
-    store, the illegal address)."""
+    flag's code under-pads the hazards (in k_pack_batch's weight job the quotient i / cols_pad is a row
+    index: an out-of-range store, the illegal address)."""
     src = os.path.join(ROOT, "tests", "kernels", "t_waitcnt_hazard.hip")
     res = {}
     for name, extra in (("plain", []), ("forcezero", ["-mllvm", "-amdgpu-waitcnt-forcezero"])):
