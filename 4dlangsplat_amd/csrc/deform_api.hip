@@ -8,7 +8,6 @@
 #include "../../include/lsr.h"
 #include "../../include/lsr_deform.h"
 #include "lsr_internal.h"
-#include <cstdlib>
 #include <vector>
 
 static_assert(lsr::DEF_UNPACK_MAX == 6 * LSR_DEFORM_MAX_SCALES, "one unpack slot per plane");
@@ -266,37 +265,20 @@ lsr::LangDeformArgs lang_args(const lsr_deform_net* net, const void* workspace, 
     return a;
 }
 
-// backward scratch: saved activations, then deform_replicas(P) copies of the packed gradient planes
-constexpr int kGradReplicas = 16;   // the most LSR_DEFORM_REPLICAS may ask for
-// Replica count of a call (every copy is zeroed and summed by the unpack, 9.5 MB each for the Neu3D
-// planes).  LSR_DEFORM_REPLICAS overrides (diagnostic A/B).
-int deform_replicas(size_t P) {
-    static const int forced = [] {
-        const char* e = std::getenv("LSR_DEFORM_REPLICAS");
-        return e ? std::max(1, std::min(kGradReplicas, std::atoi(e))) : 0;
-    }();
-    if (forced) return forced;
-    // measured (tools/gpu.sh deform_ab): 4 copies backward 12.20 vs 12.22 ms at 2M (the atomics do
-    // not contend more), configs[4] stand-in 159 vs 139-152 iterations/s at 100k (less to zero and sum);
-    // with the time planes through x-rows (round 5, tools/gpu.sh deform_ab) 2 copies 10.08 vs 10.12
-    // ms at 2M and 1.257-1.261 vs 1.257-1.273 ms per configs[4] iteration, 8 copies 10.10-10.19 / 1.29
-    (void)P;
-    return 2;
-}
+// backward scratch: saved activations, then kGradReplicas copies of the packed gradient planes
+// (every copy is zeroed and summed by the unpack, 9.5 MB each for the Neu3D planes).
+// measured (tools/gpu.sh deform_ab): 4 copies backward 12.20 vs 12.22 ms at 2M (the atomics do
+// not contend more), configs[4] stand-in 159 vs 139-152 iterations/s at 100k (less to zero and sum);
+// with the time planes through x-rows (round 5, tools/gpu.sh deform_ab) 2 copies 10.08 vs 10.12
+// ms at 2M and 1.257-1.261 vs 1.257-1.273 ms per configs[4] iteration, 8 copies 10.10-10.19 / 1.29
+constexpr int kGradReplicas = 2;
 struct BwdScratch {
     size_t X, A[LSR_DEFORM_MAX_DEPTH], dH[LSR_DEFORM_MAX_DEPTH];
     size_t Grot, Gcoff, U0, U1, U2, dv, dZ2l, dZ1l, daabb, dplanes, trow, total;
 };
 // the time planes' x-rows (DeformBwdArgs.trow): copies, their floats, each plane's offset (-1: not a
-// time plane).  LSR_DEFORM_TIME_ROWS=0 turns them off (A/B).
+// time plane)
 constexpr int kTimeRowReps = 32;
-int time_row_reps() {   // LSR_DEFORM_TIME_ROWS=n (A/B): n copies, 0 = off
-    static const int reps = [] {
-        const char* e = std::getenv("LSR_DEFORM_TIME_ROWS");
-        return e ? std::max(0, std::min(256, std::atoi(e))) : kTimeRowReps;
-    }();
-    return reps;
-}
 size_t time_row_floats(const lsr_deform_net* net, int64_t* toff) {
     size_t o = 0;
     for (int s = 0; s < net->n_scales; ++s)
@@ -335,9 +317,9 @@ BwdScratch bwd_scratch(const lsr_deform_net* net, size_t P) {
     }
     s.daabb = take(lsr::DEF_AABB_SLOTS * 16);   // zeroed with the gradient planes (contiguous)
     s.dplanes = o;
-    o += (size_t)deform_replicas(P) * layout(net).planes_end;   // the count every call of this process uses
+    o += (size_t)kGradReplicas * layout(net).planes_end;
     s.trow = o;                                                  // zeroed with the planes (contiguous)
-    o += align256((size_t)time_row_reps() * time_row_floats(net, nullptr) * f);
+    o += align256((size_t)kTimeRowReps * time_row_floats(net, nullptr) * f);
     s.total = o;
     return s;
 }
@@ -462,10 +444,10 @@ extern "C" int lsr_deform_backward(const lsr_deform_net* net, const void* worksp
     b.dplanes = fp(S.dplanes);
     b.daabb = grads->aabb;
     b.daabb_part = fp(S.daabb);
-    b.replicas = deform_replicas((size_t)P);
+    b.replicas = kGradReplicas;
     b.plane_stride = (int64_t)(L.planes_end / sizeof(float));
-    b.trow_reps = time_row_reps();
-    b.trow = b.trow_reps ? fp(S.trow) : nullptr;
+    b.trow_reps = kTimeRowReps;
+    b.trow = fp(S.trow);
     b.trow_stride = (int64_t)time_row_floats(net, b.toff);
     if (hipMemsetAsync(sc + S.daabb, 0, S.total - S.daabb, st) != hipSuccess)
         return lsr::fail(LSR_EHIP, "memset");

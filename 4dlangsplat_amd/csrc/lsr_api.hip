@@ -569,6 +569,34 @@ int count_views(int32_t n_views, const lsr_settings* const* s, const lsr_fwd_in*
                       : instance_scan_views(n_views, in, geom, host_counts, mapped, st, s[0]->debug);
 }
 
+// The preprocess backward's Gaussian-side inputs and gradient outputs for rows [r0, r0 + n) (gout
+// already addresses row r0), for lsr_backward and the batched entry points alike.
+lsr::PreprocessBwdViewsArgs preprocess_bwd_args(const lsr_settings* s, const lsr_fwd_in* in, const lsr_bwd_out* gout,
+                                                size_t r0, int n, int nv) {
+    lsr::PreprocessBwdViewsArgs a{};
+    a.P = n; a.M = in->M; a.nv = nv; a.scale_modifier = s->scale_modifier;
+    a.means3D = in->means3D + 3 * r0;
+    a.scales = in->scales ? in->scales + 3 * r0 : nullptr;
+    a.rotations = in->rotations ? in->rotations + 4 * r0 : nullptr;
+    a.shs = in->shs ? in->shs + (size_t)in->M * 3 * r0 : nullptr;
+    a.cov3D_precomp = in->cov3D_precomp ? in->cov3D_precomp + 6 * r0 : nullptr;
+    a.dopacity = gout->dL_dopacity;
+    a.dmeans3D = gout->dL_dmeans3D; a.dmeans2D = gout->dL_dmeans2D; a.dcolors = gout->dL_dcolors;
+    a.dcov3D = gout->dL_dcov3D; a.dsh = in->shs ? gout->dL_dsh : nullptr; a.dscales = gout->dL_dscales;
+    a.drots = gout->dL_drotations;
+    return a;
+}
+// One view's camera, with its geometry rows and summed records from row r0.
+void view_cam(lsr::ViewCam& c, const lsr_settings* s, const Geom& g, const float* acc_small, size_t r0) {
+    c.view = s->viewmatrix; c.proj = s->projmatrix; c.campos = s->campos;
+    c.tanfovx = s->tanfovx; c.tanfovy = s->tanfovy;
+    c.focal_x = focal(s->image_width, s->tanfovx);
+    c.focal_y = focal(s->image_height, s->tanfovy);
+    c.deg = s->sh_degree;
+    c.tiles = g.tiles + r0; c.clamped = g.clamped + r0;
+    c.acc_small = acc_small + lsr::ACC_PITCH * r0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -868,25 +896,13 @@ int lsr_backward(const lsr_settings* s, const lsr_fwd_in* in, const lsr_bwd_in* 
         }
         LSR_LAUNCHED("render backward", st, s->debug);
     }
-    lsr::PreprocessBwdArgs a{};
-    a.P = P; a.M = in->M; a.deg = s->sh_degree;
-    a.tanfovx = s->tanfovx; a.tanfovy = s->tanfovy;
-    a.focal_x = focal(W, s->tanfovx);
-    a.focal_y = focal(H, s->tanfovy);
-    a.scale_modifier = s->scale_modifier;
-    a.means3D = in->means3D; a.scales = in->scales; a.rotations = in->rotations; a.shs = in->shs;
-    a.cov3D_precomp = in->cov3D_precomp; a.view = s->viewmatrix; a.proj = s->projmatrix; a.campos = s->campos;
-    a.tiles = g.tiles;
-    a.clamped = g.clamped;
+    lsr::PreprocessBwdViewsArgs a = preprocess_bwd_args(s, in, gout, 0, P, 1);
+    view_cam(a.cam[0], s, g, sc.acc_small, 0);
     a.rec = sc.rec; a.flags = sc.flags; a.inst_off = g.inst_off; a.recq = recq;
-    a.deterministic = det; a.acc_small = sc.acc_small;
-    a.dopacity = gout->dL_dopacity;
-    a.dmeans3D = gout->dL_dmeans3D; a.dmeans2D = gout->dL_dmeans2D; a.dcolors = gout->dL_dcolors;
-    a.dcov3D = gout->dL_dcov3D; a.dsh = in->shs ? gout->dL_dsh : nullptr; a.dscales = gout->dL_dscales;
-    a.drots = gout->dL_drotations;
+    a.deterministic = det;
     {
         PhaseTimer t(LSR_PHASE_PREPROCESS_BWD, st);
-        lsr::launch_preprocess_bwd(a, accumulate != 0, st);
+        lsr::launch_preprocess_bwd_views(a, accumulate != 0, true, st);
         if (Ceff > 0 && det)
             lsr::launch_reduce_lang(P, C, lsr::lang_pad(C), recq, sc.rec, sc.flags, g.inst_off, g.tiles,
                                     gout->dL_dlanguage_feature, accumulate != 0, st);
@@ -966,38 +982,18 @@ int lsr_backward_preprocess_views_rows(int32_t n_views, const lsr_settings* cons
     const int P = in->P, n = row_count;
     const size_t r0 = (size_t)row_begin;
     if (n == 0) return LSR_OK;
-    const int M = in->M;
     // one launch per LSR_MAX_VIEWS views: Gaussian rows read and gradient rows written once; a row
     // range is the same kernel over pointers advanced to row_begin (gout already addresses it)
     for (int v0 = 0; v0 < n_views; v0 += lsr::LSR_MAX_VIEWS) {
         const int nv = std::min(lsr::LSR_MAX_VIEWS, n_views - v0);
-        lsr::PreprocessBwdViewsArgs a{};
-        a.P = n; a.M = M; a.nv = nv; a.scale_modifier = s[0]->scale_modifier;
-        a.means3D = in->means3D + 3 * r0;
-        a.scales = in->scales ? in->scales + 3 * r0 : nullptr;
-        a.rotations = in->rotations ? in->rotations + 4 * r0 : nullptr;
-        a.shs = in->shs ? in->shs + (size_t)M * 3 * r0 : nullptr;
-        a.cov3D_precomp = in->cov3D_precomp ? in->cov3D_precomp + 6 * r0 : nullptr;
+        lsr::PreprocessBwdViewsArgs a = preprocess_bwd_args(s[0], in, gout, r0, n, nv);
         for (int j = 0; j < nv; ++j) {
-            const int v = v0 + j;
-            const lsr_settings* sv = s[v];
-            Geom g = carve_geom(const_cast<void*>(geom[v]), (size_t)P, nullptr);
-            lsr::ViewCam& c = a.cam[j];
-            c.view = sv->viewmatrix; c.proj = sv->projmatrix; c.campos = sv->campos;
-            c.tanfovx = sv->tanfovx; c.tanfovy = sv->tanfovy;
-            c.focal_x = focal(sv->image_width, sv->tanfovx);
-            c.focal_y = focal(sv->image_height, sv->tanfovy);
-            c.deg = sv->sh_degree;
-            c.tiles = g.tiles + r0; c.clamped = g.clamped + r0;
-            c.acc_small = reinterpret_cast<const float*>(g.acc) + lsr::ACC_PITCH * r0;
+            Geom g = carve_geom(const_cast<void*>(geom[v0 + j]), (size_t)P, nullptr);
+            view_cam(a.cam[j], s[v0 + j], g, reinterpret_cast<const float*>(g.acc), r0);
         }
-        a.dopacity = gout->dL_dopacity;
-        a.dmeans3D = gout->dL_dmeans3D; a.dmeans2D = gout->dL_dmeans2D; a.dcolors = gout->dL_dcolors;
-        a.dcov3D = gout->dL_dcov3D; a.dsh = in->shs ? gout->dL_dsh : nullptr; a.dscales = gout->dL_dscales;
-        a.drots = gout->dL_drotations;
         {
             PhaseTimer t(LSR_PHASE_PREPROCESS_BWD_VIEWS, st);
-            lsr::launch_preprocess_bwd_views(a, accumulate != 0 || v0 > 0, st);
+            lsr::launch_preprocess_bwd_views(a, accumulate != 0 || v0 > 0, false, st);
         }
         LSR_LAUNCHED("preprocess backward (views)", st, s[0]->debug);
     }

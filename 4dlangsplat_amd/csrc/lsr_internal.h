@@ -101,42 +101,10 @@ struct PreprocessArgs {
     PreprocessView v[LSR_MAX_VIEWS];
 };
 
-struct PreprocessBwdArgs {
-    int P, M, deg;
-    float tanfovx, tanfovy, focal_x, focal_y, scale_modifier;
-    const float* means3D;
-    const float* scales;
-    const float* rotations;
-    const float* shs;
-    const float* cov3D_precomp;
-    const float* view;
-    const float* proj;
-    const float* campos;
-    const uint32_t* tiles;    // tiles touched (0 = culled; same as radii == 0)
-    const uint8_t* clamped;
-    // per-(Gaussian, tile) records of the compositor backward (render_bwd.hip), contiguous per
-    // Gaussian from inst_off[g]; flags[e] = 1 where the record was written
-    const float* rec;
-    const uint8_t* flags;
-    const uint32_t* inst_off;
-    int recq;
-    int deterministic;
-    const float* acc_small;   // atomic mode: [P, ACC_PITCH] summed records
-    // outputs (nullable)
-    float* dopacity;
-    float* dmeans3D;
-    float* dmeans2D;
-    float* dcolors;
-    float* dcov3D;
-    float* dsh;
-    float* dscales;
-    float* drots;
-};
-
-// Preprocess backward of several views of the same Gaussians in one pass (lsr_backward_views):
-// per Gaussian, the view-independent rows (mean, scale, rotation, SH) are read once, each view's
-// screen-space sums (acc_small of its compositor backward) are pushed through that view's camera,
-// and the summed gradient rows are written (or accumulated) once.
+// Preprocess backward of one or several views of the same Gaussians in one pass (lsr_backward,
+// lsr_backward_views): per Gaussian, the view-independent rows (mean, scale, rotation, SH) are read
+// once, each view's screen-space sums (acc_small of its compositor backward) are pushed through
+// that view's camera, and the summed gradient rows are written (or accumulated) once.
 struct ViewCam {
     const float* view;
     const float* proj;
@@ -145,7 +113,7 @@ struct ViewCam {
     int deg;
     const uint32_t* tiles;    // tiles touched in this view (0 = culled)
     const uint8_t* clamped;
-    const float* acc_small;   // [P, ACC_PITCH] the view's summed records
+    const float* acc_small;   // [P, ACC_PITCH] the view's summed records (atomic mode)
 };
 struct PreprocessBwdViewsArgs {
     int P, M, nv;
@@ -164,8 +132,16 @@ struct PreprocessBwdViewsArgs {
     float* dsh;
     float* dscales;
     float* drots;
+    // one view, deterministic (lsr_backward): instead of acc_small, the per-(Gaussian, tile) records
+    // of the compositor backward (render_bwd.hip), contiguous per Gaussian from inst_off[g];
+    // flags[e] = 1 where the record was written
+    const float* rec;
+    const uint8_t* flags;
+    const uint32_t* inst_off;
+    int recq;
+    int deterministic;
 };
-void launch_preprocess_bwd_views(const PreprocessBwdViewsArgs& a, bool accumulate, hipStream_t st);
+void launch_preprocess_bwd_views(const PreprocessBwdViewsArgs& a, bool accumulate, bool one_view, hipStream_t st);
 
 void launch_language_split(int P, const float* lang, uint16_t* out, hipStream_t st);
 void launch_radii_max(int P, int n, const int* const* radii, int* out, bool accumulate, hipStream_t st);
@@ -391,7 +367,6 @@ void launch_lang_deform_fwd(const LangDeformArgs& a, hipStream_t st);
 void launch_lang_deform_bwd(const LangDeformArgs& a, hipStream_t st);
 
 void launch_preprocess(const PreprocessArgs& a, hipStream_t st);
-void launch_preprocess_bwd(const PreprocessBwdArgs& a, bool accumulate, hipStream_t st);
 void launch_reduce_lang(int P, int C, int cpad, int recq, const float* rec, const uint8_t* flags,
                         const uint32_t* inst_off, const uint32_t* tiles, float* dlang, bool accumulate, hipStream_t st);
 void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t st);

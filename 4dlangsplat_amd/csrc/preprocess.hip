@@ -635,150 +635,13 @@ __device__ __forceinline__ void write_rows(float* __restrict__ dst, const float*
     }
 }
 
-template <bool ACC, int MS>
-__global__ void __launch_bounds__(256) k_preprocess_bwd(PreprocessBwdArgs a) {
-#pragma clang fp contract(fast)   // backward: gradients only, fma contraction allowed
-    constexpr int M3 = MS * 3, SP = M3 + 1;
-    __shared__ float s_sh[MS > 0 ? 256 * SP : 1];
-    __shared__ uint8_t s_vis[256];
-    const int g0 = blockIdx.x * blockDim.x;
-    const int rows = min(256, a.P - g0);
-    const int i = g0 + threadIdx.x;
-    const uint32_t ntile = i < a.P ? a.tiles[i] : 0u;
-    const bool vis = ntile > 0;
-    const bool stage = MS > 0 && a.shs != nullptr;
-    if (stage) {
-        s_vis[threadIdx.x] = vis ? 1 : 0;
-        __syncthreads();
-        stage_visible_rows<M3>(s_sh, a.shs + (size_t)g0 * M3, rows, s_vis);
-        __syncthreads();
-    }
-    if (i < a.P && (vis || !ACC)) {
-        // sum the compositor's per-(Gaussian, tile) records: contiguous per Gaussian
-        float rs[12];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) rs[k] = 0.0f;
-        if (vis && !a.deterministic) {
-            const float4* r4 = reinterpret_cast<const float4*>(a.acc_small + (size_t)i * ACC_PITCH);
-#pragma unroll
-            for (int k4 = 0; k4 < 3; ++k4) {
-                const float4 v = r4[k4];
-                rs[4 * k4] = v.x; rs[4 * k4 + 1] = v.y; rs[4 * k4 + 2] = v.z; rs[4 * k4 + 3] = v.w;
-            }
-        } else if (vis) {
-            const uint32_t e0 = a.inst_off[i];
-            for (uint32_t e = e0; e < e0 + ntile; ++e) {
-                if (!a.flags[e]) continue;
-                const float4* r4 = reinterpret_cast<const float4*>(a.rec + (size_t)e * a.recq);
-#pragma unroll
-                for (int k4 = 0; k4 < 3; ++k4) {
-                    const float4 v = r4[k4];
-                    rs[4 * k4] += v.x; rs[4 * k4 + 1] += v.y; rs[4 * k4 + 2] += v.z; rs[4 * k4 + 3] += v.w;
-                }
-            }
-        }
-        // record layout: rgb 0-2, depth 3, mean2D 4-5 (NDC), conic 6-8 (upstream x, y, w), opacity 9
-        const float3 gcol = make_float3(rs[0], rs[1], rs[2]);
-        const float gx = rs[4], gy = rs[5];
-        if (a.dmeans2D) { put<ACC>(a.dmeans2D + 3 * (size_t)i, gx); put<ACC>(a.dmeans2D + 3 * (size_t)i + 1, gy); put<ACC>(a.dmeans2D + 3 * (size_t)i + 2, 0.0f); }
-        if (a.dcolors) { put<ACC>(a.dcolors + 3 * (size_t)i, gcol.x); put<ACC>(a.dcolors + 3 * (size_t)i + 1, gcol.y); put<ACC>(a.dcolors + 3 * (size_t)i + 2, gcol.z); }
-        if (a.dopacity) put<ACC>(a.dopacity + i, rs[9]);
-
-        float3 dm = make_float3(0.0f, 0.0f, 0.0f);
-        float dcov[6] = {0, 0, 0, 0, 0, 0};
-        float3 dscale = make_float3(0.0f, 0.0f, 0.0f);
-        float4 drot = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        const int M = a.M;
-        float* srow = stage ? s_sh + threadIdx.x * SP : nullptr;
-        if (vis) {
-            const float3 p = make_float3(a.means3D[3 * i], a.means3D[3 * i + 1], a.means3D[3 * i + 2]);
-            float c3[6];
-            float3 sc = make_float3(0.0f, 0.0f, 0.0f);
-            float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (a.cov3D_precomp) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) c3[k] = a.cov3D_precomp[6 * (size_t)i + k];
-            } else {
-                sc = make_float3(a.scales[3 * i], a.scales[3 * i + 1], a.scales[3 * i + 2]);
-                q = reinterpret_cast<const float4*>(a.rotations)[i];
-                cov3d(sc, a.scale_modifier, q, c3);
-            }
-            cov2d_bwd(p, c3, a.focal_x, a.focal_y, a.tanfovx, a.tanfovy, a.view, make_float3(rs[6], rs[7], rs[8]), dm, dcov);
-            // projection of the mean
-            const float* pm = a.proj;
-            const float4 mh = xform4x4(pm, p);
-            const float mw = __builtin_amdgcn_rcpf(mh.w + 0.0000001f);
-            const float mul1 = mh.x * mw * mw;
-            const float mul2 = mh.y * mw * mw;
-            dm.x += (pm[0] * mw - pm[3] * mul1) * gx + (pm[1] * mw - pm[3] * mul2) * gy;
-            dm.y += (pm[4] * mw - pm[7] * mul1) * gx + (pm[5] * mw - pm[7] * mul2) * gy;
-            dm.z += (pm[8] * mw - pm[11] * mul1) * gx + (pm[9] * mw - pm[11] * mul2) * gy;
-            // depth row
-            const float gd = rs[3];
-            dm.x += a.view[2] * gd;
-            dm.y += a.view[6] * gd;
-            dm.z += a.view[10] * gd;
-            // SH
-            if (a.shs) {
-                const float3 dir_orig = make_float3(p.x - a.campos[0], p.y - a.campos[1], p.z - a.campos[2]);
-                const float sum2 = dir_orig.x * dir_orig.x + dir_orig.y * dir_orig.y + dir_orig.z * dir_orig.z;
-                const float il = __builtin_amdgcn_rsqf(sum2);   // gradients only: hardware rsq
-                const float x = dir_orig.x * il, y = dir_orig.y * il, z = dir_orig.z * il;
-                const uint8_t cl = a.clamped[i];
-                const float dR[3] = {(cl & 1) ? 0.0f : gcol.x, (cl & 2) ? 0.0f : gcol.y, (cl & 4) ? 0.0f : gcol.z};
-                const float* sh = stage ? srow : a.shs + (size_t)i * M * 3;
-                float* dsh = stage ? srow : (a.dsh ? a.dsh + (size_t)i * M * 3 : nullptr);
-                const int deg = a.deg;
-                float dLdx, dLdy, dLdz;
-                sh_bwd_dirsum(sh, deg, x, y, z, dR, dLdx, dLdy, dLdz);
-                // every coefficient has been read: overwrite the staged row with the gradient
-                float bs[16];
-                sh_bwd_basis(deg, x, y, z, bs);
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    if (stage) {
-#pragma unroll
-                        for (int k = 0; k < MS; ++k) dsh[k * 3 + ch] = k < 16 ? bs[k] * dR[ch] : 0.0f;
-                    } else if (dsh) {
-                        for (int k = 0; k < M; ++k) put<ACC>(dsh + k * 3 + ch, k < 16 ? bs[k] * dR[ch] : 0.0f);
-                    }
-                }
-                const float3 v = dir_orig;
-                const float invsum32 = il * il * il;
-                dm.x += ((sum2 - v.x * v.x) * dLdx - v.y * v.x * dLdy - v.z * v.x * dLdz) * invsum32;
-                dm.y += (-v.x * v.y * dLdx + (sum2 - v.y * v.y) * dLdy - v.z * v.y * dLdz) * invsum32;
-                dm.z += (-v.x * v.z * dLdx - v.y * v.z * dLdy + (sum2 - v.z * v.z) * dLdz) * invsum32;
-            }
-            if (!a.cov3D_precomp) cov3d_bwd(sc, a.scale_modifier, q, dcov, dscale, drot);
-        } else if (stage) {
-#pragma unroll
-            for (int k = 0; k < M3; ++k) srow[k] = 0.0f;
-        } else if (a.dsh && !ACC) {
-            float* dsh = a.dsh + (size_t)i * M * 3;
-            for (int k = 0; k < 3 * M; ++k) dsh[k] = 0.0f;
-        }
-        if (a.dmeans3D) { put<ACC>(a.dmeans3D + 3 * (size_t)i, dm.x); put<ACC>(a.dmeans3D + 3 * (size_t)i + 1, dm.y); put<ACC>(a.dmeans3D + 3 * (size_t)i + 2, dm.z); }
-        if (a.dcov3D) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) put<ACC>(a.dcov3D + 6 * (size_t)i + k, dcov[k]);
-        }
-        if (a.dscales) { put<ACC>(a.dscales + 3 * (size_t)i, dscale.x); put<ACC>(a.dscales + 3 * (size_t)i + 1, dscale.y); put<ACC>(a.dscales + 3 * (size_t)i + 2, dscale.z); }
-        if (a.drots) {
-            put<ACC>(a.drots + 4 * (size_t)i, drot.x); put<ACC>(a.drots + 4 * (size_t)i + 1, drot.y);
-            put<ACC>(a.drots + 4 * (size_t)i + 2, drot.z); put<ACC>(a.drots + 4 * (size_t)i + 3, drot.w);
-        }
-    }
-    if (stage && a.dsh) {   // coalesced write-out of the block's SH gradient rows
-        __syncthreads();
-        write_rows<ACC, M3>(a.dsh + (size_t)g0 * M3, s_sh, rows, s_vis);
-    }
-}
-
-// Several views at once (lsr_backward_views): the same per-view chain as k_preprocess_bwd, summed
-// over the views in which the Gaussian has tiles.  The view-independent work is done once: the
-// Gaussian's rows are read once, cov3D is built once, and the scale / rotation backward runs once
-// on the summed dL/dcov3D (it is linear in it); the gradient rows are written once.
-template <bool ACC, int MS>
+// Up to NV views at once: the per-view chain, summed over the views in which the Gaussian has
+// tiles.  The view-independent work is done once: the Gaussian's rows are read once, cov3D is built
+// once, and the scale / rotation backward runs once on the summed dL/dcov3D (it is linear in it);
+// the gradient rows are written once.  NV = LSR_MAX_VIEWS serves lsr_backward_views; NV = 1 serves
+// lsr_backward, whose deterministic mode sums the compositor's per-(Gaussian, tile) records in
+// instance order instead of reading the view's atomically summed acc_small.
+template <bool ACC, int MS, int NV>
 __global__ void __launch_bounds__(256) k_preprocess_bwd_views(PreprocessBwdViewsArgs a) {
 #pragma clang fp contract(fast)   // backward: gradients only, fma contraction allowed
     constexpr int M3 = MS * 3, SP = M3 + 1;
@@ -789,7 +652,7 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd_views(PreprocessBwdViews
     const int i = g0 + threadIdx.x;
     uint32_t vmask = 0;
 #pragma unroll
-    for (int v = 0; v < LSR_MAX_VIEWS; ++v)
+    for (int v = 0; v < NV; ++v)
         if (v < a.nv && i < a.P && a.cam[v].tiles[i] > 0) vmask |= 1u << v;
     const bool vis = vmask != 0;
     const bool stage = MS > 0 && a.shs != nullptr;
@@ -825,15 +688,36 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd_views(PreprocessBwdViews
             }
             const float* sh = stage ? srow : (a.shs ? a.shs + (size_t)i * M * 3 : nullptr);
 #pragma unroll
-            for (int v = 0; v < LSR_MAX_VIEWS; ++v) {
+            for (int v = 0; v < NV; ++v) {
                 if (!((vmask >> v) & 1u)) continue;
                 const ViewCam& cm = a.cam[v];
+                // record layout: rgb 0-2, depth 3, mean2D 4-5 (NDC), conic 6-8 (upstream x, y, w), opacity 9
                 float rs[12];
-                const float4* r4 = reinterpret_cast<const float4*>(cm.acc_small + (size_t)i * ACC_PITCH);
+                bool summed = true;
+                if constexpr (NV == 1) {
+                    if (a.deterministic) {   // the Gaussian's records, contiguous from inst_off[i], in order
+                        summed = false;
 #pragma unroll
-                for (int k4 = 0; k4 < 3; ++k4) {
-                    const float4 t = r4[k4];
-                    rs[4 * k4] = t.x; rs[4 * k4 + 1] = t.y; rs[4 * k4 + 2] = t.z; rs[4 * k4 + 3] = t.w;
+                        for (int k = 0; k < 12; ++k) rs[k] = 0.0f;
+                        const uint32_t e0 = a.inst_off[i];
+                        for (uint32_t e = e0; e < e0 + cm.tiles[i]; ++e) {
+                            if (!a.flags[e]) continue;
+                            const float4* r4 = reinterpret_cast<const float4*>(a.rec + (size_t)e * a.recq);
+#pragma unroll
+                            for (int k4 = 0; k4 < 3; ++k4) {
+                                const float4 t = r4[k4];
+                                rs[4 * k4] += t.x; rs[4 * k4 + 1] += t.y; rs[4 * k4 + 2] += t.z; rs[4 * k4 + 3] += t.w;
+                            }
+                        }
+                    }
+                }
+                if (summed) {
+                    const float4* r4 = reinterpret_cast<const float4*>(cm.acc_small + (size_t)i * ACC_PITCH);
+#pragma unroll
+                    for (int k4 = 0; k4 < 3; ++k4) {
+                        const float4 t = r4[k4];
+                        rs[4 * k4] = t.x; rs[4 * k4 + 1] = t.y; rs[4 * k4 + 2] = t.z; rs[4 * k4 + 3] = t.w;
+                    }
                 }
                 gcol[0] += rs[0]; gcol[1] += rs[1]; gcol[2] += rs[2];
                 const float gx = rs[4], gy = rs[5];
@@ -912,37 +796,28 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd_views(PreprocessBwdViews
     }
 }
 
-void launch_preprocess_bwd_views(const PreprocessBwdViewsArgs& a, bool accumulate, hipStream_t st) {
+template <bool ACC, int NV>
+static void go_pbwd(const PreprocessBwdViewsArgs& a, hipStream_t st) {
+    const dim3 grid((a.P + 255) / 256), block(256);
+    switch (a.shs ? a.M : 0) {   // SH rows staged in LDS for the usual coefficient counts
+        case 1: hipLaunchKernelGGL((k_preprocess_bwd_views<ACC, 1, NV>), grid, block, 0, st, a); break;
+        case 4: hipLaunchKernelGGL((k_preprocess_bwd_views<ACC, 4, NV>), grid, block, 0, st, a); break;
+        case 9: hipLaunchKernelGGL((k_preprocess_bwd_views<ACC, 9, NV>), grid, block, 0, st, a); break;
+        case 16: hipLaunchKernelGGL((k_preprocess_bwd_views<ACC, 16, NV>), grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL((k_preprocess_bwd_views<ACC, 0, NV>), grid, block, 0, st, a); break;
+    }
+}
+
+// one_view: the NV = 1 instantiation (lsr_backward; the only one that reads the deterministic records)
+void launch_preprocess_bwd_views(const PreprocessBwdViewsArgs& a, bool accumulate, bool one_view, hipStream_t st) {
     if (a.P == 0 || a.nv == 0) return;
-    const dim3 grid((a.P + 255) / 256), block(256);
-#define LSR_GOV(ACC, MS) hipLaunchKernelGGL((k_preprocess_bwd_views<ACC, MS>), grid, block, 0, st, a)
-    const int m = a.shs ? a.M : 0;
-    if (accumulate) {
-        switch (m) { case 1: LSR_GOV(true, 1); break; case 4: LSR_GOV(true, 4); break; case 9: LSR_GOV(true, 9); break;
-                     case 16: LSR_GOV(true, 16); break; default: LSR_GOV(true, 0); break; }
+    if (one_view) {
+        if (accumulate) go_pbwd<true, 1>(a, st);
+        else go_pbwd<false, 1>(a, st);
     } else {
-        switch (m) { case 1: LSR_GOV(false, 1); break; case 4: LSR_GOV(false, 4); break; case 9: LSR_GOV(false, 9); break;
-                     case 16: LSR_GOV(false, 16); break; default: LSR_GOV(false, 0); break; }
+        if (accumulate) go_pbwd<true, LSR_MAX_VIEWS>(a, st);
+        else go_pbwd<false, LSR_MAX_VIEWS>(a, st);
     }
-#undef LSR_GOV
-}
-
-template <bool ACC>
-static void go_pbwd(const PreprocessBwdArgs& a, hipStream_t st) {
-    const dim3 grid((a.P + 255) / 256), block(256);
-    switch (a.shs ? a.M : 0) {
-        case 1: hipLaunchKernelGGL((k_preprocess_bwd<ACC, 1>), grid, block, 0, st, a); break;
-        case 4: hipLaunchKernelGGL((k_preprocess_bwd<ACC, 4>), grid, block, 0, st, a); break;
-        case 9: hipLaunchKernelGGL((k_preprocess_bwd<ACC, 9>), grid, block, 0, st, a); break;
-        case 16: hipLaunchKernelGGL((k_preprocess_bwd<ACC, 16>), grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL((k_preprocess_bwd<ACC, 0>), grid, block, 0, st, a); break;
-    }
-}
-
-void launch_preprocess_bwd(const PreprocessBwdArgs& a, bool accumulate, hipStream_t st) {
-    if (a.P == 0) return;
-    if (accumulate) go_pbwd<true>(a, st);
-    else go_pbwd<false>(a, st);
 }
 
 // Language-feature gradient: sum of the records' C channels of each Gaussian.  A Gaussian's

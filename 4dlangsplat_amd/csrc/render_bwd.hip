@@ -1,4 +1,6 @@
-// render_bwd.hip -- backward of the compositing.
+// render_bwd.hip -- backward of the compositing, one workgroup per tile.
+// This kernel serves the deterministic mode (every channel count) and the atomic mode with 64
+// language channels; atomic calls with at most 32 channels run render_bwd_wave.hip.
 //
 // Replays each tile's list back to front, as upstream, from the last contributor: T is
 // recovered by T / (1 - alpha); dL/dalpha uses the accum_rec recurrence; the 0.99 clamp is
@@ -211,10 +213,18 @@ __global__ void __launch_bounds__(256) k_render_bwd(RenderBwdArgs a) {
     }
 }
 
-template <int CPAD, int BATCH, int Q>
+// Batches of 32 entries.  The atomic kernel exists for 64 channels only: launch_render_bwd sends
+// every atomic call with fewer to the wave kernel.
+template <int CPAD, int Q>
 static void go_bwd(const RenderBwdArgs& a, hipStream_t st) {
-    if (a.deterministic) hipLaunchKernelGGL((k_render_bwd<CPAD, (BATCH > 32 ? 32 : BATCH), Q, true>), dim3(a.grid_x * a.grid_y), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_render_bwd<CPAD, BATCH, Q, false>), dim3(a.grid_x * a.grid_y), dim3(256), 0, st, a);
+    const dim3 grid(a.grid_x * a.grid_y), block(256);
+    if constexpr (CPAD == 64) {
+        if (!a.deterministic) {
+            hipLaunchKernelGGL((k_render_bwd<CPAD, 32, Q, false>), grid, block, 0, st, a);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_render_bwd<CPAD, 32, Q, true>), grid, block, 0, st, a);
 }
 
 void launch_render_bwd(const RenderBwdArgs& a, hipStream_t st) {
@@ -224,12 +234,12 @@ void launch_render_bwd(const RenderBwdArgs& a, hipStream_t st) {
         return;
     }
     switch (lang_pad(C)) {               // deterministic records, or 64 channels
-        case 0: go_bwd<0, 64, 16>(a, st); break;
-        case 4: go_bwd<4, 64, 16>(a, st); break;
-        case 8: go_bwd<8, 64, 32>(a, st); break;
-        case 16: go_bwd<16, 64, 32>(a, st); break;
-        case 32: go_bwd<32, 64, 64>(a, st); break;
-        default: go_bwd<64, 32, 128>(a, st); break;
+        case 0: go_bwd<0, 16>(a, st); break;
+        case 4: go_bwd<4, 16>(a, st); break;
+        case 8: go_bwd<8, 32>(a, st); break;
+        case 16: go_bwd<16, 32>(a, st); break;
+        case 32: go_bwd<32, 64>(a, st); break;
+        default: go_bwd<64, 128>(a, st); break;
     }
 }
 

@@ -64,15 +64,11 @@ __device__ __forceinline__ int g_off(int p, int q) { return p * 32 + 8 * (q ^ ((
 // C = 0: the RGB-only training and render.py passes): the F rows, MFMA1, the language half of
 // MFMA-W and its staging and atomics are compiled out, and the 64 VGPRs of B fragments they hold
 // with them, so the instantiation targets twice the occupancy.
-#ifndef LSR_BWD_WAVES
-#define LSR_BWD_WAVES 2   // waves per SIMD the register budget targets
-#endif
-#ifndef LSR_BWD_WAVES_NOL
-#define LSR_BWD_WAVES_NOL 3
-#endif
+constexpr int BWD_WAVES = 2;   // waves per SIMD the register budget targets
+constexpr int BWD_WAVES_NOL = 3;
 template <bool C32, bool PRE, bool NOL>
 __global__ void __launch_bounds__(64)
-__attribute__((amdgpu_waves_per_eu(NOL ? LSR_BWD_WAVES_NOL : LSR_BWD_WAVES, NOL ? LSR_BWD_WAVES_NOL : LSR_BWD_WAVES)))
+__attribute__((amdgpu_waves_per_eu(NOL ? BWD_WAVES_NOL : BWD_WAVES, NOL ? BWD_WAVES_NOL : BWD_WAVES)))
 k_render_bwd_wave(RenderBwdBatch ab) {
     const RenderBwdArgs& a = ab.v[blockIdx.y];   // grid row = view
 #ifdef LSR_BWD_STAMPS
@@ -314,15 +310,6 @@ k_render_bwd_wave(RenderBwdBatch ab) {
     int acnt = 0;   // entries staged
     auto issue_atomics = [&]() {
         if (acnt == 0) return;
-#ifdef LSR_BWD_ABL_LANGONLY   // timing ablation only: the language rows' atomics, not the small rows'
-        constexpr bool kSmall = false;
-#else
-        constexpr bool kSmall = true;
-#endif
-#ifdef LSR_BWD_ABL_NOATOMIC   // timing ablation only (no gradients): the atomics' share
-        acnt = 0;
-        return;
-#endif
         // every staged value and row offset read from LDS first (one wait), then the atomics
         const int ch = lane & 31, q = lane & 15;
         float lv[WG / 2], sv[WG / 4];
@@ -352,7 +339,7 @@ k_render_bwd_wave(RenderBwdBatch ab) {
         }
 #pragma unroll
         for (int r = 0; r < WG / 4; ++r)
-            if (kSmall && (lane >> 4) + 4 * r < acnt && q < 10 && sv[r] != 0.0f) atomicAdd(at32(a.acc_small, so[r]), sv[r]);
+            if ((lane >> 4) + 4 * r < acnt && q < 10 && sv[r] != 0.0f) atomicAdd(at32(a.acc_small, so[r]), sv[r]);
         acnt = 0;
     };
 
@@ -450,29 +437,6 @@ k_render_bwd_wave(RenderBwdBatch ab) {
         } else if (e0 > 0) {
             pin = ld_pair(e0);
         }
-#ifdef LSR_BWD_SCALAR
-        // A/B variant: the pair's alpha / dot arithmetic as scalar VALU (no packed-fp32 hazard nops
-        // between the dependent steps of the exp chain; build with -fno-slp-vectorize)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int e = e0 + u;
-            const float Xu = u ? pin.X.y : pin.X.x, Yu = u ? pin.Y.y : pin.Y.x;
-            const float power = gauss_power(u ? pin.A.y : pin.A.x, u ? pin.B.y : pin.B.x, u ? pin.Cc.y : pin.Cc.x,
-                                            Xu - pxf, Yu - pyf);
-            const float ge = expf_repro(power);
-            const float al = fminf(0.99f, (u ? pin.O.y : pin.O.x) * ge);
-            float d = (u ? pin.R.y : pin.R.x) * g0;
-            d = __builtin_fmaf(u ? pin.Gc.y : pin.Gc.x, g1, d);
-            d = __builtin_fmaf(u ? pin.Bc.y : pin.Bc.x, g2, d);
-            d = __builtin_fmaf(u ? pin.D.y : pin.D.x, gD, d);
-            act[u] = (u ? pin.kk.y : pin.kk.x) < last_contributor && power <= 0.0f && al >= 1.0f / 255.0f;
-            alv[u] = act[u] ? al : 0.0f;
-            Gv[u] = ge;
-            romv[u] = __builtin_amdgcn_rcpf(1.0f - alv[u]);
-            dotv[u] = d + S[e];
-        }
-        if (false)
-#endif
         {
             const lsr_f2 X = pin.X, Y = pin.Y, A = pin.A, B = pin.B, Cc = pin.Cc, O = pin.O;
             const uint2 kk = pin.kk;

@@ -83,14 +83,12 @@ __device__ unsigned long long g_fwd_stamps[8];
 __device__ unsigned long long g_fwd_count[5];
 #endif
 
-#ifndef LSR_FWD_WAVES
-#define LSR_FWD_WAVES 4   // waves per SIMD the register budget targets (3: 0.293 ms, 4: 0.268 ms)
-#endif
+constexpr int FWD_WAVES = 4;   // waves per SIMD the register budget targets (3: 0.293 ms, 4: 0.268 ms)
 // PRE: C == 32 with the language rows' bf16 hi / lo made once per batch (a.lang_split).  A variant
 // that gathered every read of the group loop by LDS-DMA ran a wave's loop in 0.85x the cycles but
 // was no faster (the waves then contend for issue); it was removed in round 3.
 template <bool PRE>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LSR_FWD_WAVES, LSR_FWD_WAVES)))
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FWD_WAVES, FWD_WAVES)))
 k_render_fwd_wave_mfma(RenderFwdBatch ab) {
     const RenderFwdArgs& a = ab.v[blockIdx.y];   // grid row = view
     // group entries, one array per field (a b64 read of a pair = one packed-fp32 operand): centre
@@ -177,15 +175,6 @@ k_render_fwd_wave_mfma(RenderFwdBatch ab) {
             if (8 * o < cnt && !__all(done)) {                    // wave-uniform
                 float al[8];
                 bool ok[8];
-#ifdef LSR_FWD_SCALAR
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {   // A/B variant: scalar VALU (build with -fno-slp-vectorize)
-                    const int e = 8 * o + u;
-                    const float pw = gauss_power(s_A[e], s_B[e], s_C[e], s_X[e] - pxf, s_Y[e] - pyf);
-                    al[u] = fminf(0.99f, s_O[e] * expf_repro(pw));
-                    ok[u] = pw <= 0.0f && al[u] >= 1.0f / 255.0f;
-                }
-#else
 #pragma unroll
                 for (int u = 0; u < 8; u += 2) {   // two entries per packed-fp32 operation
                     const int e = 8 * o + u;
@@ -199,7 +188,6 @@ k_render_fwd_wave_mfma(RenderFwdBatch ab) {
                     ok[u] = pw.x <= 0.0f && al[u] >= 1.0f / 255.0f;        // padding entries: O = 0
                     ok[u + 1] = pw.y <= 0.0f && al[u + 1] >= 1.0f / 255.0f;
                 }
-#endif
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     const int e = 8 * o + u;

@@ -10,7 +10,6 @@
 // Stable tile sort of depth-ordered instances == the upstream sort of (tile << 32 | depth) keys.
 #include "lsr_common.h"
 #include "lsr_internal.h"
-#include <cstdlib>
 
 namespace lsr {
 
@@ -501,22 +500,7 @@ __global__ void __launch_bounds__(256) k_rts_scan(const SortBatch b, int pass, i
     }
 }
 
-// digits per scan block: LSR_SCAN_DG = 4 / 8 / 16 overrides (diagnostic A/B)
-static int scan_dg() {
-    static const int dg = [] {
-        const char* e = std::getenv("LSR_SCAN_DG");
-        const int v = e ? std::atoi(e) : 0;
-        return (v == 4 || v == 8 || v == 16) ? v : 16;
-    }();
-    return dg;
-}
-static void launch_rts_scan(const SortBatch& bt, int ns, int p, int items, int in_b, int nbits, hipStream_t st) {
-    switch (scan_dg()) {   // the grid covers RDX digits (groups past a pass's digits exit)
-        case 4: hipLaunchKernelGGL(k_rts_scan<4>, dim3(RDX / 4, ns), dim3(256), 0, st, bt, p, items, in_b, nbits); break;
-        case 8: hipLaunchKernelGGL(k_rts_scan<8>, dim3(RDX / 8, ns), dim3(256), 0, st, bt, p, items, in_b, nbits); break;
-        default: hipLaunchKernelGGL(k_rts_scan<16>, dim3(RDX / 16, ns), dim3(256), 0, st, bt, p, items, in_b, nbits); break;
-    }
-}
+constexpr int SCAN_DG = 16;   // digits per scan block
 
 template <int IT>
 __global__ void __launch_bounds__(256) k_rts_scatter(const SortBatch b, int pass, int in_b, int shift, int nbits_h,
@@ -675,19 +659,16 @@ int radix_sort_batch(const SortSeg* segs, int nseg, int begin_bit, int end_bit, 
     // tile sort: longer digit runs per block); swept 8 / 12 / 16 on both sorts
     // the device-planned depth sort takes 12 keys per thread: its 9-bit passes' digit runs are half
     // as long, and longer blocks win them back (depth sort 0.086-0.087 vs 0.088-0.090 ms per view
-    // at 8; LSR_DEPTH_ITEMS=8 for A/B)
-    static const int depth_items = [] {
-        const char* e = std::getenv("LSR_DEPTH_ITEMS");
-        return e && std::atoi(e) == 8 ? OS_ITEMS : 12;
-    }();
-    const int items = nmax > ((size_t)4 << 20) ? 12 : (bt.s[0].vals_c ? depth_items : OS_ITEMS);
+    // at 8)
+    const int items = (nmax > ((size_t)4 << 20) || bt.s[0].vals_c) ? 12 : OS_ITEMS;
     const unsigned nbi = (unsigned)((nmax + 256 * items - 1) / (256 * items));   // <= os_blocks: rows fit
     auto pass = [&](int p, int in_b, int shift, int nbits, int last) {
         if (items == 12)
             hipLaunchKernelGGL(k_rts_count<12>, dim3(nbi, ns), dim3(256), 0, st, bt, p, in_b, shift, nbits);
         else
             hipLaunchKernelGGL(k_rts_count<OS_ITEMS>, dim3(nbi, ns), dim3(256), 0, st, bt, p, in_b, shift, nbits);
-        launch_rts_scan(bt, ns, p, items, in_b, nbits, st);
+        // the grid covers RDX digits (groups past a pass's digits exit)
+        hipLaunchKernelGGL(k_rts_scan<SCAN_DG>, dim3(RDX / SCAN_DG, ns), dim3(256), 0, st, bt, p, items, in_b, nbits);
         if (items == 12)
             hipLaunchKernelGGL(k_rts_scatter<12>, dim3(nbi, ns), dim3(256), 0, st, bt, p, in_b, shift, nbits, last);
         else

@@ -10,10 +10,18 @@ tenth of the visible colour channels clamped at 0).  Long scene (cases L*): 6000
 scaled by L_OPACITY, so that pixels saturate late: the largest n_contrib exceeds 1024, at least 8
 fills of the wave kernel's 128-entry FIFO.  Upstream gradients are standard normal for colour,
 language and depth; the background is (0.3, 0.6, 0.9).
+
+Preprocess-backward scenes (PP_CASES, tests/test_preprocess_bwd_branches_gpu.py): the base scene's
+edits on PP_P = 700 Gaussians -- three 256-row blocks of the per-Gaussian kernel, the last one
+partial (188 rows), the first one holding the 40 culled rows next to visible ones -- with 3 language
+channels and the launcher branch under test: M SH coefficients per Gaussian (the first M of the
+scene's 16 at the degree they allow; M = 25 appends 9 rows the degree-3 colour never reads),
+colors_precomp instead of SH, or cov3D_precomp instead of scales and rotations.
 """
 import functools
 
 import numpy as np
+import torch
 
 import oracle
 import synthetic
@@ -51,30 +59,49 @@ CASES = {
 }
 
 
+PP_P = 700
+PP_CASES = {
+    "M1": dict(M=1, sh_degree=0),
+    "M4": dict(M=4, sh_degree=1),
+    "M9": dict(M=9, sh_degree=2),
+    "M16": dict(M=16),
+    "M25": dict(M=25),
+    "COL": dict(colors=True),
+    "COV": dict(cov3D=True),
+}
+
+
 class Case:
     def __init__(self, name):
-        spec = CASES[name]
+        pp = name in PP_CASES
+        spec = dict(seed=1, C=3, **PP_CASES[name]) if pp else CASES[name]
         self.name, self.C = name, spec["C"]
         self.sh_degree = spec.get("sh_degree", 3)
         self.scale_modifier = spec.get("scale_modifier", 1.0)
         self.long, self.precomp = spec.get("long", False), spec.get("precomp", False)
-        seed = sorted(CASES).index(name)
+        self.cov3D = self.precomp or spec.get("cov3D", False)
+        seed = 100 + sorted(PP_CASES).index(name) if pp else sorted(CASES).index(name)
         if self.long:
             self.W, self.H = LONG_W, LONG_H
             sc, cam = small_case(P=6000, W=self.W, H=self.H, C=self.C, seed=12, logscale_mean=-1.5, big_frac=0.0)
             sc.opacities *= L_OPACITY
         else:
             self.W, self.H = BASE_W, BASE_H
-            sc, cam = small_case(P=1500, W=self.W, H=self.H, C=self.C, seed=spec["seed"], big_frac=0.05)
+            sc, cam = small_case(P=PP_P if pp else 1500, W=self.W, H=self.H, C=self.C, seed=spec["seed"],
+                                 big_frac=0.05)
             sc.means3D[:40, 2] = -1.0
             sc.opacities[::9] = 0.999
             sc.scales[::9] *= 3.0
             sc.shs[::3, 0, :] -= 1.5
+            M = spec.get("M", 16)
+            if M != 16:
+                extra = torch.randn(sc.P, max(M - 16, 0), 3, generator=torch.Generator().manual_seed(seed)) * 0.1
+                sc.shs = torch.cat([sc.shs[:, :M], extra], dim=1).contiguous()
         self.scene = sc
         nv = spec.get("views", 0)
         self.cams = synthetic.camera_batch(nv, self.W, self.H, seed=31) if nv else [cam]
         rng = np.random.default_rng(700 + seed)
-        self.colors = rng.uniform(0, 1, (sc.P, 3)).astype(np.float32) if self.precomp else None
+        self.colors = rng.uniform(0, 1, (sc.P, 3)).astype(np.float32) if self.precomp or spec.get("colors") else None
         shape = (self.H, self.W)
         self.gcol = [rng.normal(size=(3,) + shape).astype(np.float32) for _ in self.cams]
         self.glang = [rng.normal(size=(self.C,) + shape).astype(np.float32) if self.C else None for _ in self.cams]
@@ -83,7 +110,7 @@ class Case:
     def run_kw(self):
         """keywords of lsr_testutil.run_native / run_oracle"""
         return dict(bg=BG, sh_degree=self.sh_degree, scale_modifier=self.scale_modifier,
-                    use_precomp_cov=self.precomp, colors_precomp=self.colors)
+                    use_precomp_cov=self.cov3D, colors_precomp=self.colors)
 
 
 @functools.lru_cache(maxsize=None)
@@ -102,11 +129,14 @@ class Reference:
         for v, cam in enumerate(c.cams):
             s = oracle_settings(cam, bg=BG, sh_degree=c.sh_degree, scale_modifier=c.scale_modifier)
             kw = {}
-            if c.precomp:
+            if c.cov3D:
                 kw["cov3D_precomp"] = oracle.cov3d(sc.scales.numpy(), sc.rotations.numpy())
+            else:
+                kw["scales"], kw["rotations"] = sc.scales.numpy(), sc.rotations.numpy()
+            if c.colors is not None:
                 kw["colors_precomp"] = c.colors
             else:
-                kw["scales"], kw["rotations"], kw["shs"] = sc.scales.numpy(), sc.rotations.numpy(), sc.shs.numpy()
+                kw["shs"] = sc.shs.numpy()
             r = oracle.forward(s, sc.means3D.numpy(), sc.opacities.numpy(), lang=sc.lang.numpy() if c.C else None,
                                double=double, **kw)
             g = r.backward(c.gcol[v], c.glang[v], c.gdep[v][0])
@@ -183,3 +213,25 @@ def check_preconditions(name, ref):
     if c.precomp:
         assert np.abs(ref.grads["cov3D"]).max() > 0 and np.abs(ref.grads["colors"]).max() > 0
     return out
+
+
+def check_preprocess_preconditions(name, ref):
+    """What a PP_CASES scene must give the per-Gaussian kernel's 256-row blocks, asserted on the
+    oracle's state: a last block that is partial, a block with culled and visible rows side by
+    side, SH colour channels clamped at 0 where SH is evaluated.  Returns the measured figures."""
+    c, st = case(name), ref.views[0].state()
+    P = c.scene.P
+    vis = st["tiles"] > 0
+    mixed = [b for b in range(0, P, 256) if vis[b:b + 256].any() and not vis[b:b + 256].all()]
+    fig = dict(P=P, last_block_rows=P % 256, visible=int(vis.sum()), mixed_blocks=len(mixed))
+    assert 256 < P < 1000 and P % 256 != 0 and mixed and vis[P - P % 256:].any(), (name, fig)
+    assert not vis[:40].any() and vis[40:256].any(), (name, fig)
+    if c.colors is None:
+        assert c.scene.shs.shape[1] == PP_CASES[name].get("M", 16) >= (c.sh_degree + 1) ** 2, name
+        fig["clamped_fraction"] = float(st["clamped"][vis].mean())
+        assert fig["clamped_fraction"] >= 0.05, (name, fig)
+    else:
+        assert np.abs(ref.grads["colors"]).max() > 0, name
+    if c.cov3D:
+        assert np.abs(ref.grads["cov3D"]).max() > 0, name
+    return fig

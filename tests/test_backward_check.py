@@ -9,6 +9,9 @@ tests/test_backward_branches_gpu.py (bwd_cases), on the oracle alone.
     are upper limits for a kernel that shares the float oracle's projection bit for bit.
 (b) every scene's preconditions hold (bwd_cases.check_preconditions): clamped colour channels,
     capped alphas, a quadrant wholly outside the image, long replays.
+    The preprocess-backward scenes (bwd_cases.PP_CASES, tests/test_preprocess_bwd_branches_gpu.py)
+    hold theirs (check_preprocess_preconditions): P mod 256 != 0, culled and visible rows in one
+    256-row block, clamped SH colours; the oracle takes every one of them, M = 25 included.
 (c) the check has teeth: gradients doctored on the contributing Gaussians with the smallest terms
     -- language rows zeroed, one language channel zeroed, opacity sign flipped; as many Gaussians,
     in ascending order of A, as the tensor-wide measure lets through, at least 1 in 100 -- pass
@@ -36,6 +39,11 @@ def test_f32_oracle_passes_against_f64(name):
 @pytest.mark.parametrize("name", list(bwd_cases.CASES))
 def test_scene_preconditions(name):
     print(name, bwd_cases.check_preconditions(name, bwd_cases.reference(name)))
+
+
+@pytest.mark.parametrize("name", list(bwd_cases.PP_CASES))
+def test_preprocess_scene_preconditions(name):
+    print(name, bwd_cases.check_preprocess_preconditions(name, bwd_cases.reference(name)))
 
 
 def _smallest_terms(A, change, fmax):

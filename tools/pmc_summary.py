@@ -22,7 +22,7 @@ def short(name):
 # bench phase -> the one kernel it launches (non-deterministic backward)
 PHASE_KERNEL = {"preprocess": "k_preprocess", "emit": "k_emit", "tile_ranges": "k_tile_ranges",
                 "render_fwd": "k_render_fwd_wave_mfma", "render_bwd": "k_render_bwd_wave",
-                "preprocess_bwd": "k_preprocess_bwd", "preprocess_bwd_views": "k_preprocess_bwd_views"}
+                "preprocess_bwd_views": "k_preprocess_bwd_views"}
 
 # the instantiations bench.py's timed step launches (C = 32, language operands split per batch)
 BENCH_INSTANCE = {"render_fwd": ("k_render_fwd_wave_mfma<true>",),
