@@ -655,6 +655,12 @@ int radix_sort_batch(const SortSeg* segs, int nseg, int begin_bit, int end_bit, 
     for (int i = 1; i < ns; ++i)
         if ((bt.s[i].vals_c == nullptr) != (bt.s[0].vals_c == nullptr)) return -1;
     if (bt.s[0].vals_c && (begin_bit != 0 || end_bit != 32)) return -1;
+    // a planned segment needs kept (the later passes' key count) and the gather: without the gather
+    // the three-pass plan's last pass would read and write keys_a from different blocks
+    for (int i = 0; i < ns; ++i) {
+        const SortSeg& g = bt.s[i];
+        if (g.vals_c && !(g.kept && g.gather.rect && g.gather.counts && g.gather.rect_sorted)) return -1;
+    }
     // keys per thread: 8 (2M keys: more, shorter blocks), 12 above 4M keys (the 6M-instance
     // tile sort: longer digit runs per block); swept 8 / 12 / 16 on both sorts
     // the device-planned depth sort takes 12 keys per thread: its 9-bit passes' digit runs are half
@@ -696,7 +702,10 @@ bool radix_sort_pairs(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint
                       uint32_t* vals_c) {
     if (n == 0 || end_bit <= begin_bit) return false;
     SortSeg sg{keys_a, vals_a, keys_b, vals_b, temp, kept, gather ? *gather : SortGather{nullptr, nullptr, nullptr}, n};
-    sg.vals_c = (vals_c && kept && gather && begin_bit == 0 && end_bit == 32) ? vals_c : nullptr;
+    sg.vals_c = (vals_c && kept && sg.gather.rect && sg.gather.counts && sg.gather.rect_sorted && begin_bit == 0 &&
+                 end_bit == 32)
+                    ? vals_c
+                    : nullptr;
     return radix_sort_batch(&sg, 1, begin_bit, end_bit, st) == 1;   // one segment: never mixed
 }
 
