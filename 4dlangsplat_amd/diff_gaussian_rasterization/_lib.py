@@ -132,6 +132,10 @@ SIGNATURES = {
     "lsr_l1_loss_views": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp]),
     "lsr_l1_loss_views_backward": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp,
                                                   _vp]),
+    "lsr_image_loss_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32] * 4),
+    "lsr_image_loss_views": (ctypes.c_int, [ctypes.c_int32] * 4 + [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    "lsr_image_loss_views_backward": (ctypes.c_int, [ctypes.c_int32] * 4 + [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp,
+                                                                             _vp, _vp]),
     "lsr_seg_loss_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32] * 4),
     "lsr_seg_loss_views": (ctypes.c_int, [ctypes.c_int32] * 4 + [ctypes.POINTER(SegView), ctypes.c_float,
                                           ctypes.c_float, ctypes.c_int32, _vp, _vp, _vp]),

@@ -16,8 +16,10 @@ optimizer.step() skips its freshly built nn.Parameters; the deformation field st
 The deformation field's parameters get their own Adam (their groups in training_setup,
 scene/gaussian_model.py:273-276) and are repacked after every update.  Regularisers the reference
 adds nothing here: its TV / time-smoothness term is gated on `stage == "fine"` (train.py:331), which
-never equals the stage names it runs ('fine-base', 'fine-lang'), and lambda_dssim defaults to 0
-(arguments/__init__.py:146), so the base-stage loss is the L1 alone.
+never equals the stage names it runs ('fine-base', 'fine-lang').  lambda_dssim defaults to 0
+(arguments/__init__.py:146), where the base-stage loss is the L1 alone; TrainStep(lambda_dssim=...) adds the
+reference's lambda_dssim * (1 - ssim(images, gts)) (train.py:335-337) in every stage, the L1 and the SSIM of the
+renders from one fused forward and one fused backward (image_loss.image_loss_views).
 set_reference_lr() installs the per-iteration learning-rate schedules of
 gaussian_model.py:302-330 (xyz, deformation MLPs, grid planes; OptimizationParams defaults).
 
@@ -152,7 +154,8 @@ class TrainStep:
     def __init__(self, trainer: GaussianTrainer, field=None, deform_lr: float = 1.6e-4, grid_lr: float = 1.6e-3,
                  bg: Optional[torch.Tensor] = None, stage: str = "fine-base", sh_degree: int = 3,
                  densify: Optional[Callable[[GaussianTrainer, int], None]] = None, batch_views: bool = True,
-                 joint_train: bool = False, lam: float = 0.2, beta: float = 0.01, addcosloss: bool = False):
+                 joint_train: bool = False, lam: float = 0.2, beta: float = 0.01, addcosloss: bool = False,
+                 lambda_dssim: float = 0.0):
         """densify(trainer, iteration): optional densify / prune / reset_opacity schedule, run
         between the densification statistics and the optimizer step (train.py:388-421).
         batch_views: the batch's views share one deformation-field launch (render_views)
@@ -162,13 +165,20 @@ class TrainStep:
         backward 1.45 vs 1.74 ms per iteration); round 3 had measured the opposite
         (127.8 vs 140.5) while those atomics serialised.
         joint_train, lam, beta, addcosloss: the 'lang' stages' switches (train.py --joint_coarse /
-        --joint_fine, --lam 0.2, --beta 0.01, env addcosloss)."""
+        --joint_fine, --lam 0.2, --beta 0.01, env addcosloss).
+        lambda_dssim: train.py's --lambda_dssim (OptimizationParams; upstream 3DGS trains with 0.2).  0, the
+        default, leaves loss() on the path it had without the switch.  Otherwise the loss gains
+        lambda_dssim * (1 - ssim(renders, gts[:, :3])) as train.py:335-337 adds it in every stage: a constant
+        in a 'lang' stage without joint_train, whose renders carry no gradient.  The reference passes its
+        ground truth unsliced there, and with a 4-channel ground truth its grouped convolution raises;
+        gts[:, :3], the slice its L1 takes, is the only reading that runs."""
         if joint_train and "lang" not in stage:
             raise ValueError("joint_train needs a 'lang' stage (train.py:103-104)")
         if "lang" in stage and "language_feature" not in trainer.params:
             raise ValueError("a 'lang' stage trains the language features: the trainer needs a language_feature group")
         self.trainer, self.field, self.stage = trainer, field, stage
         self.joint_train, self.lam, self.beta, self.addcosloss = joint_train, lam, beta, addcosloss
+        self.lambda_dssim = float(lambda_dssim)
         self.coff = []              # the last iteration's renders' coff (train.py:240-247)
         self.batch_views = batch_views
         self.densify = densify
@@ -250,6 +260,9 @@ class TrainStep:
         from the segment maps and feature tables (segment_lang_loss)."""
         self._one_supervision_form(gt_lang, lang_mask, lang_sup)
         if not self.lang_stage:
+            if self.lambda_dssim != 0:
+                from image_loss import image_loss_views
+                return image_loss_views([o["render"] for o in outs], gts, self.lambda_dssim)[0]
             return l1_loss_views([o["render"] for o in outs], gts)
         if lang_sup is not None:
             from language_supervision import segment_lang_loss
@@ -263,6 +276,14 @@ class TrainStep:
             loss = self.lam * (a - b).abs().mean()
             if self.addcosloss:
                 loss = loss + self.beta * (1 - torch.nn.functional.cosine_similarity(a, b, dim=-1).mean())
+        if self.lambda_dssim != 0:
+            from image_loss import image_loss_views
+            if gts is None:
+                raise ValueError("lambda_dssim needs the ground-truth images gts")
+            # with joint_train the L1 and the SSIM of one fused call; without it the renders carry no gradient
+            # and the term is a constant (only its value enters the loss)
+            total, _, ss = image_loss_views([o["render"] for o in outs], gts, self.lambda_dssim)
+            return loss + (total if self.joint_train else self.lambda_dssim * (1.0 - ss))
         if self.joint_train:
             images = torch.stack([o["render"] for o in outs])
             loss = loss + (images - gts[:, :3]).abs().mean()

@@ -19,6 +19,8 @@
  *       -> lsr_activate, lsr_activate_backward
  *   - the base stages' L1 image loss                         train.py:272-276
  *       -> lsr_l1_loss_views, lsr_l1_loss_views_backward
+ *   - the same with its D-SSIM term, and the squared error of PSNR      train.py:335-337, utils/loss_utils.py:29-69
+ *       -> lsr_image_loss_views, lsr_image_loss_views_backward
  *   - the 'lang' stages' masked L1 (+ cosine) loss against table[seg]   train.py:287-292, scene/cameras.py:92-118
  *       -> lsr_seg_loss_views, lsr_seg_loss_views_backward
  *
@@ -132,6 +134,32 @@ int lsr_l1_loss_views(int32_t V, int64_t n, const float *const *images, const fl
                       float *loss, void *workspace, void *stream);
 int lsr_l1_loss_views_backward(int32_t V, int64_t n, const float *const *images, const float *gt,
                                int64_t gt_view_stride, const float *d_loss, float *const *d_images, void *stream);
+
+/* The image loss with its D-SSIM term (train.py:284,335-337: l1_loss + lambda_dssim * (1 - ssim), utils/loss_utils.py:29-69
+ * with window_size 11) over V <= 8 views of one [C, H, W] shape without stacking them: images[v] the render of
+ * view v, its ground truth at gt + v * gt_view_stride (gt_view_stride >= C H W: gts[:, :3] of a [V, 4, H, W] tensor
+ * has 4 H W).  ssim_map per pixel and plane from the five zero-padded (padding 5) correlations with the separable,
+ * normalised 11-tap Gaussian of sigma 1.5 (its float32 taps), C1 = 0.01^2, C2 = 0.03^2:
+ *   ssim_map = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)),  s = E[.] - mu^2.
+ *   stats  [V][3]: per view  mean |x - y|, mean ssim_map, mean (x - y)^2  (the last is what PSNR needs,
+ *                  utils/image_utils.py:17-38)
+ *   totals [2]:    mean |x - y| and mean ssim_map over all V views (l1_loss and ssim(size_average=True) of the
+ *                  stacked tensors)
+ * One launch for the maps and one short launch that adds the block sums in a fixed order, in double (no atomics:
+ * two calls give the same bits).  workspace >= lsr_image_loss_workspace_bytes(V, C, H, W) (-1 on invalid sizes:
+ * V outside 1..8, C, H or W < 1, V C > 65535), 16-byte aligned; the forward leaves the per-pixel partial
+ * derivatives of ssim_map towards (mu1, E[x^2], E[xy]) there (3 V C H W floats) and the backward reads them.
+ * The backward writes every element of d_images[v] once:
+ *   d_l1[0] * sign(x - y) / (V C H W)  +  d_ssim[0] * d (mean ssim_map) / d x,
+ *   d (mean ssim_map) / d x = (conv(P_mu1) + 2 x conv(P_xx) + y conv(P_xy)) / (V C H W), conv the same correlation.
+ * Either of d_l1 / d_ssim may be NULL (treated as 0).  With d_ssim NULL or a 0 behind it the maps are not read and
+ * the result is lsr_l1_loss_views_backward's bit for bit.  No alignment beyond 4 bytes is asked of the images. */
+int64_t lsr_image_loss_workspace_bytes(int32_t V, int32_t C, int32_t H, int32_t W);
+int lsr_image_loss_views(int32_t V, int32_t C, int32_t H, int32_t W, const float *const *images, const float *gt,
+                         int64_t gt_view_stride, float *stats, float *totals, void *workspace, void *stream);
+int lsr_image_loss_views_backward(int32_t V, int32_t C, int32_t H, int32_t W, const float *const *images,
+                                  const float *gt, int64_t gt_view_stride, const float *d_l1, const float *d_ssim,
+                                  float *const *d_images, const void *workspace, void *stream);
 
 /* The 'lang' stages' loss (train.py:287-292, utils/loss_utils.py:20-27) straight from the supervision files'
  * contents (scene/cameras.py:92-118), the dense ground truth never built.  One view: */
