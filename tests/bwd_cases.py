@@ -71,6 +71,23 @@ PP_CASES = {
 }
 
 
+def base_scene(seed, C, P=1500):
+    """The base scene and its origin camera (module docstring: culled, capped, clamped edits)."""
+    sc, cam = small_case(P=P, W=BASE_W, H=BASE_H, C=C, seed=seed, big_frac=0.05)
+    sc.means3D[:40, 2] = -1.0
+    sc.opacities[::9] = 0.999
+    sc.scales[::9] *= 3.0
+    sc.shs[::3, 0, :] -= 1.5
+    return sc, cam
+
+
+def long_scene(C, opacity=L_OPACITY):
+    """The long scene and its origin camera, the opacities scaled by `opacity`."""
+    sc, cam = small_case(P=6000, W=LONG_W, H=LONG_H, C=C, seed=12, logscale_mean=-1.5, big_frac=0.0)
+    sc.opacities *= opacity
+    return sc, cam
+
+
 class Case:
     def __init__(self, name):
         pp = name in PP_CASES
@@ -83,16 +100,10 @@ class Case:
         seed = 100 + sorted(PP_CASES).index(name) if pp else sorted(CASES).index(name)
         if self.long:
             self.W, self.H = LONG_W, LONG_H
-            sc, cam = small_case(P=6000, W=self.W, H=self.H, C=self.C, seed=12, logscale_mean=-1.5, big_frac=0.0)
-            sc.opacities *= L_OPACITY
+            sc, cam = long_scene(self.C)
         else:
             self.W, self.H = BASE_W, BASE_H
-            sc, cam = small_case(P=PP_P if pp else 1500, W=self.W, H=self.H, C=self.C, seed=spec["seed"],
-                                 big_frac=0.05)
-            sc.means3D[:40, 2] = -1.0
-            sc.opacities[::9] = 0.999
-            sc.scales[::9] *= 3.0
-            sc.shs[::3, 0, :] -= 1.5
+            sc, cam = base_scene(spec["seed"], self.C, P=PP_P if pp else 1500)
             M = spec.get("M", 16)
             if M != 16:
                 extra = torch.randn(sc.P, max(M - 16, 0), 3, generator=torch.Generator().manual_seed(seed)) * 0.1
@@ -187,29 +198,33 @@ def outside_quadrant_tiles(ref_view, W, H):
             (16 * (t % gx) + 8 >= W or 16 * (t // gx) + 8 >= H)]
 
 
+def view_figures(c, r, tag):
+    """One view's part of check_preconditions (c: a Case or anything with its W, H, long and
+    precomp; r: the oracle's result of the view): asserted, and returned as figures."""
+    st = r.state()
+    tiles = outside_quadrant_tiles(r, c.W, c.H)
+    assert tiles, tag
+    fig = dict(outside_quadrant_tiles=len(tiles))
+    if c.long:
+        fig["max_n_contrib"] = int(st["n_contrib"].max())
+        fig["longest_list"] = int((st["ranges"][:, 1].astype(np.int64) - st["ranges"][:, 0]).max())
+        assert fig["max_n_contrib"] > 1024 and fig["longest_list"] > 1024, (tag, fig)
+    else:
+        vis = r.radii > 0
+        assert (r.radii[:40] == 0).all() and vis.sum() > 500, tag
+        if not c.precomp:   # colors_precomp has no SH evaluation, hence no clamp
+            fig["clamped_fraction"] = float(st["clamped"][vis].mean())
+            assert fig["clamped_fraction"] >= 0.05, (tag, fig)
+        fig["capped_pairs"] = capped_pairs(r, c.W, c.H)
+        assert fig["capped_pairs"] >= 20, (tag, fig)
+    return fig
+
+
 def check_preconditions(name, ref):
     """What each scene must exercise, asserted on the oracle's state (so that a scene cannot
     silently stop reaching its branch).  Returns the measured figures."""
     c = case(name)
-    out = {}
-    for v, r in enumerate(ref.views):
-        st = r.state()
-        tiles = outside_quadrant_tiles(r, c.W, c.H)
-        assert tiles, (name, v)
-        fig = dict(outside_quadrant_tiles=len(tiles))
-        if c.long:
-            fig["max_n_contrib"] = int(st["n_contrib"].max())
-            fig["longest_list"] = int((st["ranges"][:, 1].astype(np.int64) - st["ranges"][:, 0]).max())
-            assert fig["max_n_contrib"] > 1024 and fig["longest_list"] > 1024, (name, fig)
-        else:
-            vis = r.radii > 0
-            assert (r.radii[:40] == 0).all() and vis.sum() > 500, (name, v)
-            if not c.precomp:   # colors_precomp has no SH evaluation, hence no clamp
-                fig["clamped_fraction"] = float(st["clamped"][vis].mean())
-                assert fig["clamped_fraction"] >= 0.05, (name, v, fig)
-            fig["capped_pairs"] = capped_pairs(r, c.W, c.H)
-            assert fig["capped_pairs"] >= 20, (name, v, fig)
-        out[v] = fig
+    out = {v: view_figures(c, r, (name, v)) for v, r in enumerate(ref.views)}
     if c.precomp:
         assert np.abs(ref.grads["cov3D"]).max() > 0 and np.abs(ref.grads["colors"]).max() > 0
     return out

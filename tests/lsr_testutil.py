@@ -24,8 +24,37 @@ def raster_settings(cam, bg=(1.0, 1.0, 1.0), sh_degree=3, include_feature=True, 
         include_feature=include_feature)
 
 
+class DecodedState:
+    """A forward's state as arrays, for the checks below where no native state exists (the oracle
+    standing in for the kernels on a machine without a GPU): what decode_img and decode_point_list
+    return, and the radii."""
+
+    def __init__(self, ranges, tile_max, final_T, n_contrib, point_list, radii):
+        self.ranges, self.tile_max, self.final_T, self.n_contrib = ranges, tile_max, final_T, n_contrib
+        self.point_list, self.radii = point_list, radii
+
+
+def tile_max_of(n_contrib):
+    """Per 16 x 16 tile the largest n_contrib of its pixels inside the image [tiles]."""
+    H, W = n_contrib.shape
+    gx, gy = (W + 15) // 16, (H + 15) // 16
+    pad = np.zeros((16 * gy, 16 * gx), np.int64)
+    pad[:H, :W] = n_contrib
+    return pad.reshape(gy, 16, gx, 16).max(axis=(1, 3)).reshape(-1)
+
+
+def oracle_as_native(ref):
+    """The oracle's own state in the native one's place (DecodedState), tile_max derived from its
+    n_contrib."""
+    st = ref.state()
+    return DecodedState(st["ranges"], tile_max_of(st["n_contrib"]).astype(np.uint32), st["final_T"],
+                        st["n_contrib"], st["point_list"], ref.radii)
+
+
 def decode_img(state):
     """ranges [tiles,2], tile_max [tiles], final_T [H,W], n_contrib [H,W] from the img workspace."""
+    if isinstance(state, DecodedState):
+        return state.ranges, state.tile_max, state.final_T, state.n_contrib
     W, H = state.settings.c.image_width, state.settings.c.image_height
     gx, gy = (W + 15) // 16, (H + 15) // 16
     nt = gx * gy
@@ -54,6 +83,8 @@ def decode_point_words(state):
 
 
 def decode_point_list(state):
+    if isinstance(state, DecodedState):
+        return state.point_list
     K = state.num_rendered
     W, H = state.settings.c.image_width, state.settings.c.image_height
     nt = ((W + 15) // 16) * ((H + 15) // 16)
@@ -127,7 +158,8 @@ def run_native(scene, cam, bg=(1.0, 1.0, 1.0), include_feature=True, use_precomp
 
 
 def run_oracle(scene, cam, bg=(1.0, 1.0, 1.0), include_feature=True, use_precomp_cov=False, colors_precomp=None,
-               sh_degree=3, nthreads=0, scale_modifier=1.0):
+               sh_degree=3, nthreads=0, scale_modifier=1.0, double=False, lang=None):
+    """lang: language rows to use instead of the scene's."""
     s = oracle_settings(cam, bg=bg, sh_degree=sh_degree, include_feature=include_feature,
                         scale_modifier=scale_modifier)
     kw = {}
@@ -139,8 +171,10 @@ def run_oracle(scene, cam, bg=(1.0, 1.0, 1.0), include_feature=True, use_precomp
         kw["colors_precomp"] = np.asarray(colors_precomp)
     else:
         kw["shs"] = scene.shs.numpy()
-    lang = scene.lang.numpy() if scene.lang.numel() > 0 else None
-    return oracle.forward(s, scene.means3D.numpy(), scene.opacities.numpy(), lang=lang, nthreads=nthreads, **kw)
+    if lang is None:
+        lang = scene.lang.numpy() if scene.lang.numel() > 0 else None
+    return oracle.forward(s, scene.means3D.numpy(), scene.opacities.numpy(), lang=lang, nthreads=nthreads,
+                          double=double, **kw)
 
 
 def grad_err(native, ref):
@@ -205,4 +239,130 @@ def grad_check(native, ref, abs_terms=None):
         stats[key] = st
         if off:
             bad[key] = off
+    return bad, stats
+
+
+U24 = 2.0 ** -24          # fp32 unit roundoff
+IMAGE_COEF_MAX = 1e-4     # the cap of the derived coefficient; the matrix-core language coefficient
+IMAGE_COEF_C = 8          # the constant c of image_coef
+
+
+def image_coef(k):
+    """min(1e-4, (2 k + c) 2^-24), the per-pixel coefficient of image_check for sums the kernels
+    and the float oracle both keep in fp32; k = the pixel's n_contrib.
+
+    Both sides blend the same entries with the same alpha and T bit for bit (image_check asserts the
+    equal final_T and last contributor this rests on), so they differ only in how a term
+    t = f alpha T enters the sum s, u = 2^-24, every partial sum bounded by A = sum |t|:
+      float oracle (no contraction)  fl(fl(f alpha) T): 2 u |t|;  s = fl(s + .): u |s| <= u A
+      kernel                         w = fl(alpha T):     u |t|;  s = fma(f, w, s): u |s| <= u A
+    at most 3 u |t| + 2 u A apart per blended entry, (3 + 2 n) u A over a pixel's n entries.
+    n_contrib is the list position of the last blended entry, so n <= k.  The colour then adds
+    T bg: fl(T bg) and a rounded add in the oracle, the same or one contracted fma in the kernel,
+    3 u A more (A includes T bg); language and depth have no final operation.  Two more units cover
+    what the first-order count leaves out: the second-order terms, and A taken from a rounded
+    float image (colour, depth) or from the double oracle's weights (language), either within
+    1e-5 of the exact sum.  c = 3 + 3 + 2 = 8.  The cap 1e-4 (k >= 835) is grad_check's
+    coefficient: errors of a long sum do not line up, and the reference itself is only that good
+    against the double oracle (tests/test_forward_check.py)."""
+    return np.minimum(IMAGE_COEF_MAX, (2.0 * np.asarray(k, np.float64) + IMAGE_COEF_C) * U24)
+
+
+def _np(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+def image_elements(native, ref, A, coef):
+    """One output image [c, H, W] against the reference, per element: finite, |native - ref| <=
+    coef A (coef: scalar or [H, W]), exactly 0 where A == 0.  Returns (offences, stats)."""
+    n, r, A = (np.asarray(x, np.float64) for x in (native, ref, A))
+    assert n.shape == r.shape == A.shape, (n.shape, r.shape, A.shape)
+    off, st = {}, dict(max_err_over_A=0.0, max_err_over_bound=0.0)
+    if n.size == 0:
+        return off, st
+    bound = np.broadcast_to(np.asarray(coef, np.float64), n.shape[1:])[None] * A
+    finite = np.isfinite(n)
+    err = np.where(finite, np.abs(np.where(finite, n, 0.0) - r), np.inf)
+    pos = A > 0
+    if pos.any():
+        st["max_err_over_A"] = float((err[pos] / A[pos]).max())
+        st["max_err_over_bound"] = float((err[pos] / bound[pos]).max())
+    over = ~finite | ~(err <= bound) | (~pos & (n != 0))
+    if over.any():
+        idx = np.argwhere(over)
+        off["elements"] = int(over.sum())
+        off["first"] = [(tuple(int(i) for i in ix), float(n[tuple(ix)]), float(r[tuple(ix)]), float(A[tuple(ix)]))
+                        for ix in idx[:6]]
+    return off, st
+
+
+def uses_matrix_cores(C, include_feature=True):
+    """The language sums run on k_render_fwd_wave_mfma (bf16 hi / lo products): 17..32 channels."""
+    return bool(include_feature) and 17 <= C <= 32
+
+
+def image_check(native, ref, A_lang, coef=None, exact=True):
+    """The forward counterpart of grad_check: one view's native (color, lang, depth, state) against
+    the float oracle's OracleResult `ref` of the same view.  state: a RasterizerState, or a
+    DecodedState where the oracle stands in for the kernels.
+
+    Exact: radii; final_T bit for bit; every pixel's last contributor the same Gaussian and every
+    tile list an ordered subsequence of upstream's (check_binning_against_upstream);
+    tile_max_contrib[t] == the largest native n_contrib over tile t's pixels inside the image (0
+    where none blends); no tile range left at the preset (~0, 0): a tile without entries has
+    exactly (0, 0); a pixel with n_contrib == 0 has colour bg, language 0, depth 0, final_T 1.
+
+    Per element, no floor: |native - ref| <= coef A, exactly 0 where A == 0, non-finite fails.
+    A: language -- `A_lang` [C, H, W], the double oracle's forward with |language rows| (the
+    weights do not depend on them: the sum of |f| w); colour and depth -- the oracle's own image,
+    valid because every term is non-negative (asserted: the activated colours, bg and the visible
+    depths).  coef: image_coef(native n_contrib), except 1e-4 (IMAGE_COEF_MAX, grad_check's
+    coefficient for the same arithmetic) for the language image of the matrix-core kernel, whose
+    products are bf16 hi / lo splits (~2^-16 per term) summed in fp32.  `coef` overrides both
+    (the float oracle against the double one rounds the projection too: 1e-4 throughout).
+
+    Returns (bad, stats): bad[what] describes the offences (empty: passed); stats[output] has
+    max_err_over_A and max_err_over_bound (over the elements with A > 0)."""
+    color, lang, depth, state = native
+    color, lang, depth = _np(color), _np(lang), _np(depth)
+    H, W = color.shape[1], color.shape[2]
+    C = lang.shape[0]
+    rs = ref.state()
+    bg = np.asarray(ref.settings.bg, color.dtype).reshape(3)
+    vis = ref.radii > 0
+    assert (rs["rgb"] >= 0).all() and (bg >= 0).all() and (rs["depth"][vis] > 0).all()
+    include_feature = bool(ref.settings.include_feature)
+    A_lang = np.zeros((C, H, W)) if A_lang is None else np.asarray(A_lang, np.float64)
+    assert (A_lang >= np.abs(ref.lang) * (1 - 1e-3) - 1e-30).all()       # |sum| <= sum |term|
+    bad, stats = {}, {}
+    ranges, tmax, fT, nc = decode_img(state)
+    if exact:
+        if not np.array_equal(_np(state.radii), ref.radii):
+            bad["radii"] = int((_np(state.radii) != ref.radii).sum())
+        try:
+            check_binning_against_upstream(state, rs, W, H)     # final_T, last contributors, lists
+        except (AssertionError, KeyError) as e:
+            bad["binning"] = repr(e)[:400]
+        want = tile_max_of(nc)
+        if not np.array_equal(tmax.astype(np.int64), want):
+            t = np.nonzero(tmax.astype(np.int64) != want)[0]
+            bad["tile_max_contrib"] = [(int(i), int(tmax[i]), int(want[i])) for i in t[:6]]
+        r = ranges.astype(np.int64)
+        upstream_empty = rs["ranges"][:, 0] == rs["ranges"][:, 1]
+        wrong = ((r[:, 0] >= r[:, 1]) | upstream_empty) & ((r[:, 0] != 0) | (r[:, 1] != 0))
+        if wrong.any():
+            bad["empty_tile_range"] = [(int(i), int(r[i, 0]), int(r[i, 1])) for i in np.nonzero(wrong)[0][:6]]
+        e = nc == 0
+        ok = ((color[:, e] == bg[:, None]).all() and (lang[:, e] == 0).all() and (depth[:, e] == 0).all()
+              and (fT[e] == 1).all())
+        if not ok:
+            bad["uncovered_pixels"] = int(e.sum())
+    k = image_coef(nc) if coef is None else coef
+    kl = IMAGE_COEF_MAX if coef is None and uses_matrix_cores(C, include_feature) else k
+    for name, n, r, A, cf in (("color", color, ref.color, ref.color, k), ("lang", lang, ref.lang, A_lang, kl),
+                              ("depth", depth, ref.depth, ref.depth, k)):
+        off, st = image_elements(n, r, A, cf)
+        stats[name] = st
+        if off:
+            bad[name] = off
     return bad, stats

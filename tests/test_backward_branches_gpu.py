@@ -27,7 +27,8 @@ Asserted per case: both modes pass lsr_testutil.grad_check against the float ora
 |native - ref| <= 1e-4 |ref| + 1e-4 A for language, opacity and means2D, A from the oracle's
 abs_terms; grad_err <= 1e-4 for every field); the deterministic gradients repeat bit for bit; atomic
 against deterministic per element within 1e-4 |det| + 1e-5 max|field| for the fields derived
-through the preprocess backward; the images within 1e-4 (RGB) and 1e-3 (language); equal radii; and
+through the preprocess backward; the images within 1e-4 (RGB) and 1e-3 (language) and per pixel
+through lsr_testutil.image_check (tests/test_forward_branches_gpu.py); equal radii; and
 the scene's preconditions on the oracle's state (bwd_cases.check_preconditions).
 
 Measured on an MI355X, against the float oracle (recorded, not used to set any bound; the last
@@ -81,7 +82,8 @@ if not torch.cuda.is_available():  # CPU container: the driver only runs these o
 
 import diff_gaussian_rasterization as dgr  # noqa: E402
 import bwd_cases  # noqa: E402
-from lsr_testutil import grad_check, oracle_keyed, raster_settings, run_native  # noqa: E402
+import fwd_cases  # noqa: E402
+from lsr_testutil import grad_check, image_check, oracle_keyed, raster_settings, run_native  # noqa: E402
 
 RGB_TOL, LANG_TOL = 1e-4, 1e-3
 DERIVED = ("means3D", "scales", "rotations", "sh", "cov3D", "colors")
@@ -102,12 +104,15 @@ def _forward(c, cam):
     return run_native(c.scene, cam, **c.run_kw())
 
 
-def _check_forward(c, nat, ref_view):
+def _check_forward(c, nat, ref_view, view=0):
     color, lang, radii, depth, st = nat
     np.testing.assert_array_equal(radii.cpu().numpy(), ref_view.radii)
     assert np.abs(color.cpu().numpy() - ref_view.color).max() <= RGB_TOL
     if c.C:
         assert np.abs(lang.cpu().numpy() - ref_view.lang).max() <= LANG_TOL
+    # and per pixel, with the exact state checks (tests/test_forward_branches_gpu.py)
+    bad, stats = image_check((color, lang, depth, st), ref_view, fwd_cases.lang_scale(c.name)[view])
+    assert not bad, (c.name, view, bad, stats)
 
 
 def _check_grads(c, ref, atomic, dets, label):
@@ -188,8 +193,8 @@ def test_two_views_case(name):
                                                scale_modifier=c.scale_modifier),
                                dev.means3D, dev.opacities, shs=dev.shs, language_feature=dev.lang,
                                scales=dev.scales, rotations=dev.rotations) for cam in c.cams]
-    for nat, rv in zip(nats, ref.views):
-        _check_forward(c, nat, rv)
+    for v, (nat, rv) in enumerate(zip(nats, ref.views)):
+        _check_forward(c, nat, rv, v)
     dets = []
     for _ in range(2):
         out = None
