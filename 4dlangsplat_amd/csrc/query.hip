@@ -32,6 +32,7 @@
 
 #include "../../include/lsr.h"
 #include "../../include/lsr_query.h"
+#include "lsr_mfma.h"
 
 namespace lsr {
 int fail(int code, const std::string& msg);   // lsr_api.hip (thread-local lsr_last_error)
@@ -70,9 +71,7 @@ template <int NPT> struct PixVec;
 template <> struct PixVec<4> { typedef f32x4 type; typedef LSR_LDS f32x4 lds_type; };
 template <> struct PixVec<2> { typedef f32x2 type; typedef LSR_LDS f32x2 lds_type; };
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
+using lsr::mfma4;   // lsr_mfma.h
 
 // W[row][k .. k + 3] of a [rows, in] matrix; k past `in` reads as zero (the padded first layer)
 template <bool VEC>

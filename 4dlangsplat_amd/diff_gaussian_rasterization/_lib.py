@@ -112,6 +112,12 @@ QUERY_MAX_INPUT = 32        # LSR_QUERY_MAX_INPUT
 SEGMENT_MAX_SCALE = 63      # LSR_SEGMENT_MAX_SCALE (include/lsr_segment.h)
 SEGMENT_MAX_SIDE = 16384    # LSR_SEGMENT_MAX_SIDE
 SEGMENT_STRATEGIES = {"point": 0, "mean": 1}   # LSR_SEGMENT_POINT, LSR_SEGMENT_MEAN
+PCA_MIN_CHANNELS = 4        # LSR_PCA_MIN_CHANNELS (include/lsr_pca.h)
+PCA_MAX_CHANNELS = 32       # LSR_PCA_MAX_CHANNELS
+PCA_BLOCK_PIXELS = 2048     # LSR_PCA_BLOCK_PIXELS
+PCA_TILE_PIXELS = 256       # LSR_PCA_TILE_PIXELS
+PCA_FINISH_WAVES = 16       # LSR_PCA_FINISH_WAVES
+PCA_RANGE_THREADS = 256     # LSR_PCA_RANGE_THREADS
 
 _vp = ctypes.c_void_p
 SIGNATURES = {
@@ -255,6 +261,16 @@ SIGNATURES = {
     "lsr_segment_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32] * 3),
     "lsr_segment": (ctypes.c_int, [ctypes.c_int32] * 3 + [_vp, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp,
                                    ctypes.c_int32] + [_vp] * 8),
+    "lsr_pca_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64]),
+    "lsr_pca_sums": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                    _vp, _vp, _vp]),
+    "lsr_pca_gram": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64, _vp,
+                                    ctypes.c_int64, ctypes.c_int32, _vp, _vp, _vp]),
+    "lsr_pca_basis": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64] + [_vp] * 6),
+    "lsr_pca_project": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp,
+                                       ctypes.c_int32, _vp, _vp, _vp, _vp]),
+    "lsr_pca_colorize_f32": (ctypes.c_int, [ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    "lsr_pca_colorize_u8": (ctypes.c_int, [ctypes.c_int64, _vp, _vp, _vp, _vp]),
     "lsr_profile_read": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
                                         ctypes.c_int32]),
 }

@@ -714,10 +714,17 @@ def to8b(x: np.ndarray) -> np.ndarray:
 
 def render_set(model_path: str, name: str, iteration, views, scene: GaussianScene, background: torch.Tensor,
                output_channel: str = "rgb", stage: str = "fine-lang", save_images: bool = True,
-               save_npy: bool = True, **render_kw) -> float:
+               save_npy: bool = True, pca: str = "sklearn", **render_kw) -> float:
     """render.py:67-161 without ground truth (ONLY_EVAL): renders every view, writes
     {model_path}/{name}_{output_channel}/ours_{iteration}/renders_npy/{idx:05d}.npy ([H, W, C], the
-    files eval/eval.py reads) and renders/{idx:05d}.png; returns the FPS as render.py prints it."""
+    files eval/eval.py reads) and renders/{idx:05d}.png; returns the FPS as render.py prints it.
+    pca picks how an image of more than three channels becomes a picture: "sklearn" is pca_compress
+    (the reference: host copy, a fit per frame), "native" the same per-frame fit on the device
+    (language_query.pca_image), "sequence" one language_query.LanguagePCA fitted over all rendered
+    frames, so that a video keeps its colours from frame to frame.  The two device modes copy only the
+    8-bit picture to the host."""
+    if pca not in ("sklearn", "native", "sequence"):
+        raise ValueError(f'pca must be "sklearn", "native" or "sequence", got {pca!r}')
     key = "render" if output_channel == "rgb" else "language_feature_image"
     base = os.path.join(model_path, f"{name}_{output_channel}", f"ours_{iteration}")
     render_path, npy_path = os.path.join(base, "renders"), os.path.join(base, "renders_npy")
@@ -734,11 +741,24 @@ def render_set(model_path: str, name: str, iteration, views, scene: GaussianScen
         t2 = _time.time()
     fps = (len(views) - 1) / (t2 - t1) if len(views) > 1 else float("nan")
     print("FPS:", fps)
+    as_image = (lambda r: r) if output_channel == "rgb" else (lambda r: (r + 1.0) / 2)
+    seq = None
+    if pca != "sklearn":
+        from language_query import LanguagePCA, pca_image
+        if save_images and pca == "sequence" and outs and outs[0].shape[0] > 3:
+            class _Images:                                   # walked once per sweep: one (r + 1) / 2 alive at a time
+                def __iter__(self):
+                    return (as_image(r) for r in outs)
+            seq = LanguagePCA().fit(_Images())
     for idx, r in enumerate(outs):
         if save_npy:
             np.save(os.path.join(npy_path, f"{idx:05d}.npy"), r.permute(1, 2, 0).cpu().numpy())
         if save_images:
-            img = r if output_channel == "rgb" else (r + 1.0) / 2
+            img = as_image(r)
+            if img.shape[0] > 3 and pca != "sklearn":
+                img8 = seq.transform(img, out="uint8") if seq is not None else pca_image(img, out="uint8")
+                write_png(os.path.join(render_path, f"{idx:05d}.png"), img8.cpu().numpy())
+                continue
             img = pca_compress(img).numpy() if img.shape[0] > 3 else img.permute(1, 2, 0).cpu().numpy()
             write_png(os.path.join(render_path, f"{idx:05d}.png"), to8b(img))
     return fps

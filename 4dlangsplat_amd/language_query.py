@@ -12,6 +12,10 @@ vector is never written, only n_pos floats per pixel.
 
     seg = segment(rel, gt_masks)        # masks, level scores, chosen level and IoU per phrase (activate_stream)
 
+    rgb = pca_image(render_pkg["language_feature_image"])          # [H, W, 3] in [0, 1]: render.py's pca_compress
+    pca = LanguagePCA().fit(frames)                                # one basis and one range for a whole sequence
+    rgb8 = pca.transform(frame, out="uint8")
+
 The embeddings are used as given (the reference normalises them in set_positives); there is no
 text encoder here.
 
@@ -22,6 +26,7 @@ dtype.  That fallback is the CPU implementation, and in float64 the yardstick of
 from __future__ import annotations
 
 import collections
+import collections.abc
 import ctypes
 import glob
 import os
@@ -32,7 +37,8 @@ import torch
 
 from diff_gaussian_rasterization import _lib
 
-__all__ = ["LanguageDecoder", "relevancy", "query_frames", "Segmentation", "segment", "segment_frames"]
+__all__ = ["LanguageDecoder", "relevancy", "query_frames", "Segmentation", "segment", "segment_frames", "pca_image",
+           "LanguagePCA"]
 
 
 class LanguageDecoder:
@@ -406,3 +412,172 @@ def segment_frames(level_dirs, decoder, pos_embeds, neg_embeds, out_dir, gt=None
         out["phrase_iou"] = [sum(r[k][0] for r in rows) / len(rows) if rows else float("nan") for k in range(n_pos)]
         out["mean_iou"] = sum(out["phrase_iou"]) / n_pos
     return out
+
+
+# ---- PCA colouring of language images (include/lsr_pca.h, csrc/pca.hip) --------------------------------
+def _pca_frame(frame, layout):
+    """The checks of the native PCA path: returns (C, H, W, pix_stride, chan_stride) of a frame the
+    library can address as frame[pixel * pix_stride + channel * chan_stride], or raises ValueError."""
+    if layout not in ("hwc", "chw"):
+        raise ValueError('layout must be "hwc" or "chw"')
+    if not isinstance(frame, torch.Tensor) or frame.dim() != 3:
+        raise ValueError("a frame must be a 3-dimensional tensor ([C, H, W] or [H, W, C]), got "
+                         f"{tuple(frame.shape) if isinstance(frame, torch.Tensor) else type(frame).__name__}")
+    if frame.dtype != torch.float32:
+        raise ValueError(f"the native PCA takes float32 frames, got {frame.dtype}")
+    if layout == "chw":
+        (C, H, W), (sc, sh, sw) = frame.shape, frame.stride()
+    else:
+        (H, W, C), (sh, sw, sc) = frame.shape, frame.stride()
+    if not _lib.PCA_MIN_CHANNELS <= C <= _lib.PCA_MAX_CHANNELS:
+        raise ValueError(f"the native PCA takes {_lib.PCA_MIN_CHANNELS} ... {_lib.PCA_MAX_CHANNELS} channels, the frame "
+                         f"has C = {C} (layout {layout!r}, shape {tuple(frame.shape)}); an image of three channels or "
+                         "fewer needs no PCA")
+    if H > 1 and W > 1 and sh != W * sw:
+        raise ValueError(f"the frame's pixels do not share one stride (row stride {sh}, column stride {sw}, W = {W}): "
+                         "two strides cannot describe it; pass frame.contiguous()")
+    if frame.device.type != "cuda":
+        raise ValueError(f"the native PCA runs on the GPU: the frame is on {frame.device} (a CPU tensor has no device "
+                         "pointer to hand to the kernels); move it with .cuda()")
+    return C, H, W, (sw if W > 1 else sh), sc
+
+
+class LanguagePCA:
+    """A three-component PCA of language images that stays on the device: fit() takes the mean, the
+    covariance and the value range over one frame or a whole sequence, transform() colours a frame
+    with them.  One basis for a sequence keeps the colours of a video steady, where a per-frame fit
+    (the reference's pca_compress, and pca_image here) lets axes swap and flip between frames.
+
+    After fit(): mean [C], components [3, C] (sklearn's sign rule), explained_variance [3], range [2]
+    (min and max of the projections over every fitted frame), float32 tensors on the frames' device;
+    n_samples the pixel count.  Frames are float32 CUDA tensors of 4 ... 32 channels, [C, H, W]
+    (layout "chw") or [H, W, C] ("hwc"); anything else is a ValueError."""
+
+    def __init__(self):
+        self.mean = self.components = self.explained_variance = self.range = None
+        self.n_channels = self.n_samples = None
+
+    def fit(self, frames, layout="chw"):
+        """frames: a sequence (or any re-iterable) of same-C frames.  It is walked three times (sums, centred
+        Gram, range) and a frame is only held while its sweep is enqueued, so an object whose __iter__
+        computes each frame afresh keeps one temporary alive at a time.  A one-shot iterator (a generator)
+        is put into a list first, which holds every frame for the length of the fit."""
+        self._fit(frames, layout)
+        return self
+
+    @torch.no_grad()
+    def _fit(self, frames, layout, keep_y=False):
+        """The sweeps of fit(); keep_y: return the projections [n_pix, 3] of the last frame."""
+        if isinstance(frames, collections.abc.Iterator):      # one shot: it cannot be walked again
+            frames = list(frames)
+        lib = _lib.load()
+        C = dev = ws = sums = gram = None
+        count = total = 0
+
+        def sweeps():
+            """(index, frame, geometry, n_pix, workspace pointer) of every frame, checked against the first."""
+            nonlocal ws
+            for i, f in enumerate(frames):
+                g = _pca_frame(f, layout)
+                if C is not None and (g[0] != C or f.device != dev):
+                    raise ValueError(f"the frames of one fit share the channel count and the device: got C = {g[0]} "
+                                     f"on {f.device} after C = {C} on {dev}")
+                n = g[1] * g[2]
+                need = lib.lsr_pca_workspace_bytes(g[0], n)
+                if ws is None or ws.numel() < need:
+                    ws = torch.empty(need, dtype=torch.uint8, device=f.device)
+                yield i, f.detach(), g, n, ws.data_ptr()
+
+        first = True
+        for i, f, g, n, wp in sweeps():
+            if C is None:
+                C, dev = g[0], f.device
+                acc = torch.empty(_lib.PCA_MAX_CHANNELS * (_lib.PCA_MAX_CHANNELS + 1), dtype=torch.float64, device=dev)
+                sums, gram = acc[:_lib.PCA_MAX_CHANNELS], acc[_lib.PCA_MAX_CHANNELS:]
+            count, total = i + 1, total + n
+            if n:                                             # an empty frame launches nothing
+                with torch.cuda.device(dev):
+                    _lib.check(lib.lsr_pca_sums(C, n, f.data_ptr(), g[3], g[4], int(first), sums.data_ptr(), wp,
+                                                torch.cuda.current_stream(dev).cuda_stream), "lsr_pca_sums")
+                first = False
+        if not count:
+            raise ValueError("fit() needs at least one frame")
+        if total < 2:
+            raise ValueError(f"a covariance needs at least two pixels, the frames have {total}")
+        mean = torch.empty(C, dtype=torch.float32, device=dev)
+        comps = torch.empty(3, C, dtype=torch.float32, device=dev)
+        evals = torch.empty(3, dtype=torch.float32, device=dev)
+        rng = torch.empty(2, dtype=torch.float32, device=dev)
+        y = None
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            first, seen = True, 0
+            for i, f, g, n, wp in sweeps():
+                seen += n
+                if n:
+                    _lib.check(lib.lsr_pca_gram(C, n, f.data_ptr(), g[3], g[4], sums.data_ptr(), total, int(first),
+                                                gram.data_ptr(), wp, stream), "lsr_pca_gram")
+                    first = False
+            if seen != total:
+                raise ValueError(f"the frames changed between two walks of fit(): {total} pixels, then {seen}")
+            _lib.check(lib.lsr_pca_basis(C, total, sums.data_ptr(), gram.data_ptr(), mean.data_ptr(), comps.data_ptr(),
+                                         evals.data_ptr(), stream), "lsr_pca_basis")
+            first = True
+            for i, f, g, n, wp in sweeps():
+                if not n:
+                    continue
+                last = keep_y and i == count - 1
+                if last:
+                    y = torch.empty(n, 3, dtype=torch.float32, device=dev)
+                _lib.check(lib.lsr_pca_project(C, n, f.data_ptr(), g[3], g[4], mean.data_ptr(), comps.data_ptr(),
+                                               int(first), y.data_ptr() if last else None, rng.data_ptr(), wp, stream),
+                           "lsr_pca_project")
+                first = False
+        self.mean, self.components, self.explained_variance, self.range = mean, comps, evals, rng
+        self.n_channels, self.n_samples = C, total
+        return y
+
+    def _colorize(self, y, H, W, out):
+        dev = y.device
+        img = torch.empty(H, W, 3, dtype=torch.uint8 if out == "uint8" else torch.float32, device=dev)
+        lib = _lib.load()
+        fn, what = ((lib.lsr_pca_colorize_u8, "lsr_pca_colorize_u8") if out == "uint8"
+                    else (lib.lsr_pca_colorize_f32, "lsr_pca_colorize_f32"))
+        with torch.cuda.device(dev):
+            _lib.check(fn(H * W, y.data_ptr(), self.range.data_ptr(), img.data_ptr(),
+                          torch.cuda.current_stream(dev).cuda_stream), what)
+        return img
+
+    @torch.no_grad()
+    def transform(self, frame, layout="chw", out="float"):
+        """The frame coloured with the fitted basis and range: [H, W, 3] float32 in [0, 1] (values outside
+        the fitted range are clipped), or uint8 by floor(255 x) with out="uint8", on the frame's device."""
+        if out not in ("float", "uint8"):
+            raise ValueError('out must be "float" or "uint8"')
+        if self.components is None:
+            raise ValueError("transform() before fit(): there is no basis yet")
+        C, H, W, ps, cs = _pca_frame(frame, layout)
+        if C != self.n_channels or frame.device != self.mean.device:
+            raise ValueError(f"the frame has C = {C} on {frame.device}, the basis was fitted for C = {self.n_channels} "
+                             f"on {self.mean.device}")
+        dev, n = frame.device, H * W
+        y = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        if n:                                                 # y alone: no range is taken, so no workspace either
+            with torch.cuda.device(dev):
+                _lib.check(_lib.load().lsr_pca_project(C, n, frame.detach().data_ptr(), ps, cs, self.mean.data_ptr(),
+                                                       self.components.data_ptr(), 0, y.data_ptr(), None, None,
+                                                       torch.cuda.current_stream(dev).cuda_stream), "lsr_pca_project")
+        return self._colorize(y, H, W, out)
+
+
+def pca_image(frame, layout="chw", out="float"):
+    """gaussian_scene.pca_compress without the host trip: [C, H, W] (or [H, W, C] with layout "hwc")
+    -> [H, W, 3] float32 in [0, 1], or uint8 (the reference's to8b of it) with out="uint8", on the
+    frame's device.  The same as LanguagePCA().fit([frame]).transform(frame), in three reads of the
+    frame.  A constant frame, where the reference divides 0 by 0, gives zeros."""
+    if out not in ("float", "uint8"):
+        raise ValueError('out must be "float" or "uint8"')
+    pca = LanguagePCA()
+    y = pca._fit([frame], layout, keep_y=True)
+    _, H, W, _, _ = _pca_frame(frame, layout)
+    return pca._colorize(y, H, W, out)
