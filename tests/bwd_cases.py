@@ -17,6 +17,19 @@ partial (188 rows), the first one holding the 40 culled rows next to visible one
 channels and the launcher branch under test: M SH coefficients per Gaussian (the first M of the
 scene's 16 at the degree they allow; M = 25 appends 9 rows the degree-3 colour never reads),
 colors_precomp instead of SH, or cov3D_precomp instead of scales and rotations.
+
+Two more scenes on the same 700 Gaussians with M = 16 (PP_EXTRA, explicit seeds: the seeds of
+PP_CASES come from the sorted names and must not move) reach the geometry branches no random scene
+does.  CLAMP (forward and backward): rows 40..87 are wide Gaussians (scales 0.25..0.75) at depth
+2..5 placed 1.35..1.85 tan(fov) z off the axis, alternately in x and in y -- outside the 1.3 tan(fov)
+clamp of the EWA projection yet reaching into the image, so the forward clamps t and the backward
+zeroes that Jacobian column; rows 100..149 carry five copies of FAINT_OPACITIES, around the
+opacity exp(-1e-3) / 255 below which no pixel can pass the alpha prefilter: such a Gaussian keeps
+its radius and is not listed (five copies: with four, 15 of the 16 rows of opacity <= 0.003 are
+visible, one short of what check_preprocess_preconditions asserts).  NEAR (forward only) adds six rows on the optical axis of the origin
+camera (identity view matrix: the view-space z is the stored one exactly) at and beside the near
+plane z = 0.2f; three are culled, three kept.  In double 0.2f > 0.2, the splats at z = 0.2f become
+visible and cover the image: NEAR has no meaning against the double oracle or in a backward test.
 """
 import functools
 
@@ -71,6 +84,42 @@ PP_CASES = {
 }
 
 
+# opacities around t = exp(-1e-3) / 255, skip_power's switch: at and below it no pixel passes 1 / 255
+_T = np.float32(np.exp(-1e-3) / 255.0)
+FAINT_OPACITIES = np.array([0.0, 1e-6, 0.001, 0.003, np.nextafter(_T, np.float32(0)), np.nextafter(_T, np.float32(1)),
+                            1.0 / 255.0, 0.004, 0.005, 0.01], np.float32)
+CLAMP_ROWS, FAINT_ROWS, NEAR_ROWS = slice(40, 88), slice(100, 150), slice(200, 206)
+NEAR_Z = np.array([0.2, 0.2, np.nextafter(np.float32(0.2), np.float32(1)), 0.21, 0.19999, 0.25], np.float32)
+NEAR_KEPT = NEAR_Z > np.float32(0.2)
+PP_EXTRA = {
+    "CLAMP": dict(M=16, case_seed=107, clamp=True),
+    "NEAR": dict(M=16, case_seed=108, clamp=True, near=True),
+}
+
+
+def pp_spec(name):
+    return PP_CASES[name] if name in PP_CASES else PP_EXTRA[name]
+
+
+def clamp_edits(sc, cam, near=False):
+    """The CLAMP (and NEAR) rows written into a base scene (module docstring)."""
+    g = torch.Generator().manual_seed(5)
+    n = CLAMP_ROWS.stop - CLAMP_ROWS.start
+    z = torch.rand(n, generator=g) * 3.0 + 2.0
+    off = (torch.rand(n, generator=g) * 0.5 + 1.35) * (torch.randint(0, 2, (n,), generator=g) * 2 - 1).float()
+    inside = torch.rand(n, generator=g) * 1.6 - 0.8
+    even = torch.arange(n) % 2 == 0
+    x = torch.where(even, off, inside) * cam.tanfovx * z
+    y = torch.where(even, inside, off) * cam.tanfovy * z
+    sc.means3D[CLAMP_ROWS] = torch.stack([x, y, z], dim=1)
+    sc.scales[CLAMP_ROWS] = torch.rand(n, 3, generator=g) * 0.5 + 0.25
+    sc.opacities[FAINT_ROWS] = torch.from_numpy(np.tile(FAINT_OPACITIES, 5)).reshape(-1, 1)
+    if near:
+        assert np.array_equal(cam.world_view_transform.numpy(), np.eye(4, dtype=np.float32))
+        xy = torch.tensor([[0.0, 0.0], [0.004, 0.0], [0.0, 0.004], [-0.004, 0.0], [0.0, -0.004], [0.004, 0.004]])
+        sc.means3D[NEAR_ROWS] = torch.cat([xy, torch.from_numpy(NEAR_Z)[:, None]], dim=1)
+
+
 def base_scene(seed, C, P=1500):
     """The base scene and its origin camera (module docstring: culled, capped, clamped edits)."""
     sc, cam = small_case(P=P, W=BASE_W, H=BASE_H, C=C, seed=seed, big_frac=0.05)
@@ -90,14 +139,17 @@ def long_scene(C, opacity=L_OPACITY):
 
 class Case:
     def __init__(self, name):
-        pp = name in PP_CASES
-        spec = dict(seed=1, C=3, **PP_CASES[name]) if pp else CASES[name]
+        pp = name in PP_CASES or name in PP_EXTRA
+        spec = dict(seed=1, C=3, **pp_spec(name)) if pp else CASES[name]
         self.name, self.C = name, spec["C"]
         self.sh_degree = spec.get("sh_degree", 3)
         self.scale_modifier = spec.get("scale_modifier", 1.0)
         self.long, self.precomp = spec.get("long", False), spec.get("precomp", False)
         self.cov3D = self.precomp or spec.get("cov3D", False)
-        seed = 100 + sorted(PP_CASES).index(name) if pp else sorted(CASES).index(name)
+        if "case_seed" in spec:
+            seed = spec["case_seed"]
+        else:
+            seed = 100 + sorted(PP_CASES).index(name) if pp else sorted(CASES).index(name)
         if self.long:
             self.W, self.H = LONG_W, LONG_H
             sc, cam = long_scene(self.C)
@@ -108,6 +160,8 @@ class Case:
             if M != 16:
                 extra = torch.randn(sc.P, max(M - 16, 0), 3, generator=torch.Generator().manual_seed(seed)) * 0.1
                 sc.shs = torch.cat([sc.shs[:, :M], extra], dim=1).contiguous()
+            if spec.get("clamp"):
+                clamp_edits(sc, cam, near=spec.get("near", False))
         self.scene = sc
         nv = spec.get("views", 0)
         self.cams = synthetic.camera_batch(nv, self.W, self.H, seed=31) if nv else [cam]
@@ -233,7 +287,10 @@ def check_preconditions(name, ref):
 def check_preprocess_preconditions(name, ref):
     """What a PP_CASES scene must give the per-Gaussian kernel's 256-row blocks, asserted on the
     oracle's state: a last block that is partial, a block with culled and visible rows side by
-    side, SH colour channels clamped at 0 where SH is evaluated.  Returns the measured figures."""
+    side, SH colour channels clamped at 0 where SH is evaluated.  PP_EXTRA scenes, on the float
+    oracle: at least 20 visible rows outside the 1.3 tan(fov) clamp, at least 20 of them with a
+    means3D gradient, at least 16 visible rows of opacity <= 0.003; NEAR: exactly the rows with
+    z > 0.2f of its six are kept.  Returns the measured figures."""
     c, st = case(name), ref.views[0].state()
     P = c.scene.P
     vis = st["tiles"] > 0
@@ -242,11 +299,37 @@ def check_preprocess_preconditions(name, ref):
     assert 256 < P < 1000 and P % 256 != 0 and mixed and vis[P - P % 256:].any(), (name, fig)
     assert not vis[:40].any() and vis[40:256].any(), (name, fig)
     if c.colors is None:
-        assert c.scene.shs.shape[1] == PP_CASES[name].get("M", 16) >= (c.sh_degree + 1) ** 2, name
+        assert c.scene.shs.shape[1] == pp_spec(name).get("M", 16) >= (c.sh_degree + 1) ** 2, name
         fig["clamped_fraction"] = float(st["clamped"][vis].mean())
         assert fig["clamped_fraction"] >= 0.05, (name, fig)
     else:
         assert np.abs(ref.grads["colors"]).max() > 0, name
     if c.cov3D:
         assert np.abs(ref.grads["cov3D"]).max() > 0, name
+    if name in PP_EXTRA:
+        assert not ref.views[0].double, name      # the counts below are the float oracle's
+        seen = ref.views[0].radii > 0
+        fc = frustum_clamped(c.scene, c.cams[0]) & seen
+        faint = seen & (c.scene.opacities.numpy().reshape(-1) <= np.float32(0.003))
+        moved = fc & (ref.grads["means3D"] != 0).any(axis=1)
+        fig.update(frustum_clamped=int(fc.sum()), faint_visible=int(faint.sum()), frustum_clamped_with_grad=int(moved.sum()),
+                   max_clamped_means3D_grad=float(np.abs(ref.grads["means3D"][fc]).max()))
+        assert fig["frustum_clamped"] >= 20 and fig["faint_visible"] >= 16, (name, fig)
+        assert fig["frustum_clamped_with_grad"] >= 20, (name, fig)
+        if pp_spec(name).get("near"):
+            near = seen[NEAR_ROWS]
+            fig["near_kept"] = int(near.sum())
+            assert np.array_equal(near, NEAR_KEPT) and NEAR_KEPT.sum() == 3, (name, near)
     return fig
+
+
+def frustum_clamped(scene, cam):
+    """Rows whose view-space x / z or y / z lies outside 1.3 tan(fov): the clamp of computeCov2D,
+    decided on the same float quotients as the oracle and the kernels."""
+    m = cam.world_view_transform.numpy().astype(np.float32).reshape(-1)
+    p = scene.means3D.numpy().astype(np.float32)
+    t = [m[k] * p[:, 0] + m[4 + k] * p[:, 1] + m[8 + k] * p[:, 2] + m[12 + k] for k in range(3)]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        txtz, tytz = t[0] / t[2], t[1] / t[2]
+    limx, limy = np.float32(1.3) * np.float32(cam.tanfovx), np.float32(1.3) * np.float32(cam.tanfovy)
+    return (np.abs(txtz) > limx) | (np.abs(tytz) > limy)

@@ -366,3 +366,177 @@ def image_check(native, ref, A_lang, coef=None, exact=True):
         if off:
             bad[name] = off
     return bad, stats
+
+
+# ---- the geom workspace of one view (carve_geom, lsr_api.hip) and the forward preprocess check ----
+ACC_PITCH = 16            # floats per accumulator row (lsr_internal.h)
+# (name, dtype, elements per Gaussian) in carve order; each array starts on a 256-byte boundary
+GEOM_ARRAYS = (("xy", np.float32, 2), ("conic_o", np.float32, 4), ("rgbd", np.float32, 4), ("clamped", np.uint8, 1),
+               ("tiles", np.uint32, 1), ("key_a", np.uint32, 1), ("key_b", np.uint32, 1), ("val_a", np.uint32, 1),
+               ("val_b", np.uint32, 1), ("counts", np.uint32, 1), ("offsets", np.uint32, 1), ("inst_off", np.uint32, 1),
+               ("radius", np.int32, 1), ("rect", np.uint32, 2), ("rect_sorted", np.uint32, 2))
+
+
+def rect_pack(x0, y0, x1, y1, qmap):
+    """lsr_internal.h rect_pack on arrays -> [n, 2] uint32."""
+    x0, y0, x1, y1, qmap = (np.asarray(a, np.uint32) for a in (x0, y0, x1, y1, qmap))
+    return np.stack([x0 | y0 << 12 | (qmap & 0xFF) << 24, x1 | y1 << 12 | (qmap >> 8) << 24], axis=-1).astype(np.uint32)
+
+
+def rect_unpack(rect):
+    """rect [n, 2] uint32 -> dict of int64 arrays: x0, y0, x1, y1 (rect_unpack), qmap (rect_quad_map),
+    small (rect_small), mask (rect_tile_mask of qmap), area, count (rect_count)."""
+    r = np.asarray(rect, np.uint32).astype(np.int64)
+    x0, y0, x1, y1 = r[:, 0] & 0xFFF, (r[:, 0] >> 12) & 0xFFF, r[:, 1] & 0xFFF, (r[:, 1] >> 12) & 0xFFF
+    qmap = (r[:, 0] >> 24) | (r[:, 1] >> 24) << 8
+    small = (x1 - x0 <= 2) & (y1 - y0 <= 2)
+    mask = ((qmap & 0x33) != 0) * 1 | ((qmap & 0xCC) != 0) * 2 | ((qmap & 0x3300) != 0) * 4 | ((qmap & 0xCC00) != 0) * 8
+    area = (x1 - x0) * (y1 - y0)
+    popc = np.array([bin(int(m)).count("1") for m in mask], np.int64)
+    count = np.where((area > 0) & small, popc, area)
+    return dict(x0=x0, y0=y0, x1=x1, y1=y1, qmap=qmap, small=small, mask=mask, area=area, count=count)
+
+
+def decode_geom(geom_bytes, P):
+    """One view's geom workspace (uint8 tensor or array of lsr_geom_bytes(P) bytes) as numpy arrays
+    by the layout of carve_geom: the arrays of GEOM_ARRAYS, total [4] u32, then the sort's and the
+    scan's workspaces, whose joint size is what lsr_geom_bytes(P) leaves between total and the last
+    array, acc [P, ACC_PITCH] float32.  rect also comes unpacked under "rect_fields" (rect_unpack)."""
+    raw = _np(geom_bytes).reshape(-1).view(np.uint8)
+    total_bytes = int(dgr._lib.load().lsr_geom_bytes(P))
+    assert raw.size == total_bytes, (raw.size, total_bytes)
+    out, off = {}, 0
+    for name, dt, n in GEOM_ARRAYS:
+        nb = P * n * np.dtype(dt).itemsize
+        a = raw[off:off + nb].view(dt)
+        out[name] = a.reshape(P, n) if n > 1 else a
+        off += _al(nb)
+    out["total"] = raw[off:off + 16].view(np.uint32)
+    off += _al(16)
+    acc_bytes = P * ACC_PITCH * 4
+    acc_off = total_bytes - _al(acc_bytes)
+    assert acc_off >= off and (acc_off - off) % ALIGN == 0, (off, acc_off)   # sort_tmp + scan_tmp, each aligned
+    out["tmp_bytes"] = acc_off - off
+    out["acc"] = raw[acc_off:acc_off + acc_bytes].view(np.float32).reshape(P, ACC_PITCH)
+    assert acc_off + _al(acc_bytes) == total_bytes       # the layout ends exactly at lsr_geom_bytes(P)
+    out["rect_fields"] = rect_unpack(out["rect"])
+    return out
+
+
+def upstream_rect(xy, radii, W, H):
+    """tile_rect (lsr_common.h; upstream getRect) in float32 on arrays: rmin_x, rmin_y, rmax_x, rmax_y."""
+    gx, gy = (W + 15) // 16, (H + 15) // 16
+    p, r = np.asarray(xy, np.float32), np.asarray(radii).astype(np.float32)
+    f16, f15 = np.float32(16.0), np.float32(15.0)
+
+    def clip(v, g):   # (int) truncates toward zero; clamped into [0, g]
+        return np.clip(np.trunc(np.clip(v, -1e9, 1e9)).astype(np.int64), 0, g)
+    return (clip((p[:, 0] - r) / f16, gx), clip((p[:, 1] - r) / f16, gy),
+            clip((p[:, 0] + r + f15) / f16, gx), clip((p[:, 1] + r + f15) / f16, gy))
+
+
+def _ulps(a, b):
+    """Distance of float32 arrays in units in the last place (bit patterns on the number line;
+    non-finite values count as 2^31)."""
+    def line(x):
+        i = np.asarray(x, np.float32).view(np.int32).astype(np.int64)
+        return np.where(i < 0, -(i & 0x7FFFFFFF), i)
+    d = np.abs(line(a) - line(b))
+    return np.where(np.isfinite(a) & np.isfinite(b), d, 2 ** 31)
+
+
+def preprocess_check(decoded, radii, ref, W, H, point_list=None, num_rendered=None, prefill=None):
+    """One view's forward preprocess -- `decoded` (decode_geom of its geom workspace after phase 1)
+    and the public `radii` -- against the float oracle's OracleResult `ref` of the same view.
+
+    Rows with ref.radii > 0: radii and the workspace's radius equal ref.radii; xy, conic_o (a, b,
+    c, opacity), the colour and the depth equal the oracle's bit for bit (uint32 views: -0.0 and
+    NaN differ); the clamped bits equal the oracle's.  Rows with ref.radii == 0: radii, radius,
+    tiles, both rect words and clamped are 0.
+    Every row: tiles == rect_count(rect); a non-empty rectangle lies inside upstream's 3-sigma
+    rectangle (upstream_rect of the oracle's xy and radii) and the grid; tiles <= the oracle's
+    (upstream's) count; a rectangle wider or taller than 2 tiles has a zero quadrant map.
+    Opacity <= 0.003 with a radius: tiles == 0 and rect == 0 (no pixel can pass 1 / 255; between
+    0.003 and 0.005 the switch of skip_power's fast log is no contract, above it only the rules
+    above hold).
+    acc: all ACC_PITCH floats of a row with a non-empty rectangle are zero bits; with `prefill` (the
+    byte the caller filled the workspace with) every other row still holds it.
+    num_rendered (the native instance count), when given: sum(tiles) == num_rendered.  point_list
+    (the ids of the native list's valid entries: the tile ranges' extent, the binning drops the
+    instances that reach no quadrant), when given: id i is listed at most tiles[i] times, exactly
+    tiles[i] times when its rectangle is at most 2 x 2 tiles.
+
+    Returns (bad, stats): bad[what] describes the offences (empty: passed); stats has the row counts
+    and, per float field, the number of differing elements and the largest distance in ulps."""
+    st = ref.state()
+    P = len(ref.radii)
+    vis = ref.radii > 0
+    radii = _np(radii).reshape(-1)
+    gx, gy = (W + 15) // 16, (H + 15) // 16
+    bad, stats = {}, dict(visible=int(vis.sum()))
+
+    def rows(mask):
+        return [int(i) for i in np.nonzero(mask)[0][:6]]
+
+    for name, got in (("radii", radii), ("radius", decoded["radius"])):
+        if not np.array_equal(got, ref.radii):
+            bad[name] = rows(got != ref.radii)
+    rgbd = decoded["rgbd"]
+    for name, got, want in (("xy", decoded["xy"], st["xy"]), ("conic_o", decoded["conic_o"], st["conic_o"]),
+                            ("rgb", rgbd[:, :3], st["rgb"]), ("depth", rgbd[:, 3:], st["depth"][:, None])):
+        g, w = np.ascontiguousarray(got[vis], np.float32), np.ascontiguousarray(want[vis], np.float32)
+        diff = g.view(np.uint32) != w.view(np.uint32)
+        stats[name] = dict(differing=int(diff.sum()), max_ulps=int(_ulps(g, w).max(initial=0)))
+        if diff.any():
+            ix = np.argwhere(diff)[:6]
+            bad[name] = dict(differing=int(diff.sum()), max_ulps=stats[name]["max_ulps"],
+                             first=[(int(np.nonzero(vis)[0][i]), int(k), float(g[i, k]), float(w[i, k])) for i, k in ix])
+    cl = decoded["clamped"].astype(np.int64)
+    want_cl = (st["clamped"].astype(np.int64) * np.array([1, 2, 4])).sum(axis=1)
+    if (cl != want_cl)[vis].any():
+        bad["clamped"] = rows(vis & (cl != want_cl))
+    rect, tiles = decoded["rect"], decoded["tiles"].astype(np.int64)
+    f = rect_unpack(rect)
+    for name, arr in (("radii", radii), ("radius", decoded["radius"]), ("tiles", tiles), ("rect", rect.any(axis=1)),
+                      ("clamped", cl)):
+        if (arr != 0)[~vis].any():
+            bad["culled_" + name] = rows(~vis & (arr != 0))
+    if (tiles != f["count"]).any():
+        bad["tiles_vs_rect_count"] = rows(tiles != f["count"])
+    full = f["area"] != 0
+    ux0, uy0, ux1, uy1 = upstream_rect(st["xy"], ref.radii, W, H)
+    inside = ((f["x0"] >= ux0) & (f["y0"] >= uy0) & (f["x1"] <= ux1) & (f["y1"] <= uy1) & (f["x1"] > f["x0"]) &
+              (f["y1"] > f["y0"]) & (f["x1"] <= gx) & (f["y1"] <= gy))
+    if (full & ~inside).any():
+        bad["rect_outside_upstream"] = rows(full & ~inside)
+    if (tiles > st["tiles"].astype(np.int64)).any():
+        bad["tiles_above_upstream"] = rows(tiles > st["tiles"])
+    if (~f["small"] & (f["qmap"] != 0)).any():
+        bad["map_on_large_rect"] = rows(~f["small"] & (f["qmap"] != 0))
+    opacity = st["conic_o"][:, 3]
+    faint = vis & (opacity <= np.float32(0.003))
+    if (faint & ((tiles != 0) | rect.any(axis=1))).any():
+        bad["faint_listed"] = rows(faint & ((tiles != 0) | rect.any(axis=1)))
+    accw = np.ascontiguousarray(decoded["acc"]).view(np.uint32).reshape(P, ACC_PITCH)
+    if (accw[full] != 0).any():
+        bad["acc_not_zeroed"] = rows(full & (accw != 0).any(axis=1))
+    if prefill is not None:
+        word = int(prefill) * 0x01010101
+        if (accw[~full] != word).any():
+            bad["acc_written_without_rect"] = rows(~full & (accw != word).any(axis=1))
+    stats.update(rect_rows=int(full.sum()), listed_rows=int((tiles > 0).sum()), unlisted_visible=int((vis & (tiles == 0)).sum()),
+                 faint_visible=int(faint.sum()), small_rects=int((full & f["small"]).sum()),
+                 tiles=int(tiles.sum()), upstream_tiles=int(st["tiles"].astype(np.int64).sum()))
+    if num_rendered is not None and int(tiles.sum()) != int(num_rendered):
+        bad["num_rendered"] = (int(tiles.sum()), int(num_rendered))
+    if point_list is not None:
+        ids = np.asarray(point_list).astype(np.int64)
+        if ids.size and ids.max() >= P:
+            bad["list_id_out_of_range"] = int(ids.max())
+        else:
+            n = np.bincount(ids, minlength=P)
+            wrong = (n > tiles) | (f["small"] & (n != tiles))
+            if wrong.any():
+                bad["list_counts"] = [(i, int(n[i]), int(tiles[i])) for i in rows(wrong)]
+            stats["listed_instances"] = int(n.sum())
+    return bad, stats

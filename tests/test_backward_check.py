@@ -12,6 +12,9 @@ tests/test_backward_branches_gpu.py (bwd_cases), on the oracle alone.
     The preprocess-backward scenes (bwd_cases.PP_CASES, tests/test_preprocess_bwd_branches_gpu.py)
     hold theirs (check_preprocess_preconditions): P mod 256 != 0, culled and visible rows in one
     256-row block, clamped SH colours; the oracle takes every one of them, M = 25 included.
+    CLAMP (bwd_cases.PP_EXTRA) also holds its own: at least 20 visible rows outside the
+    1.3 tan(fov) clamp, 20 of them with a means3D gradient, 16 visible rows of opacity <= 0.003
+    (its float-against-double margin: tests/test_preprocess_fwd_check.py).
 (c) the check has teeth: gradients doctored on the contributing Gaussians with the smallest terms
     -- language rows zeroed, one language channel zeroed, opacity sign flipped; as many Gaussians,
     in ascending order of A, as the tensor-wide measure lets through, at least 1 in 100 -- pass
@@ -41,7 +44,7 @@ def test_scene_preconditions(name):
     print(name, bwd_cases.check_preconditions(name, bwd_cases.reference(name)))
 
 
-@pytest.mark.parametrize("name", list(bwd_cases.PP_CASES))
+@pytest.mark.parametrize("name", list(bwd_cases.PP_CASES) + ["CLAMP"])
 def test_preprocess_scene_preconditions(name):
     print(name, bwd_cases.check_preprocess_preconditions(name, bwd_cases.reference(name)))
 

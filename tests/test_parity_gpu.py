@@ -2,7 +2,8 @@
 
 Forward contract (north star): RGB within 1e-4, language features within 1e-3 of the reference.
 Against the oracle the preprocess and the contributor decisions are bit-exact (same IEEE
-operation order, reproducible exp), so radii and final_T are compared exactly.  The native
+operation order, reproducible exp), so radii and final_T are compared exactly (the preprocess's
+per-Gaussian records themselves: tests/test_preprocess_fwd_branches_gpu.py).  The native
 binning drops instances that cannot contribute to their tile; the tile lists are checked to be
 ordered subsequences of upstream's with every dropped entry provably inactive, and every pixel's
 last contributor is the same Gaussian (check_binning_against_upstream).  Channel sums differ only

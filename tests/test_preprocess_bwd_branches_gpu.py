@@ -17,6 +17,9 @@ visible ones (tests/test_backward_check.py asserts it on the oracle).
     M25    SH, 25 coefficients, degree 3            generic, MS = 0 (rows 16..24: zero gradient)
     COL    colors_precomp, scales and rotations     generic, no SH chain
     COV    SH 16, cov3D_precomp                     staged rows, no scale / rotation backward
+    CLAMP  SH 16; 46 visible rows outside the       staged rows, MS = 16; cov2d_bwd zeroes the clamped
+           1.3 tan(fov) clamp, 19 faint rows        Jacobian column (39 such rows with a means3D
+           with a radius and no tiles               gradient, up to 117); unlisted rows: zero gradient
 
 Asserted per case: the atomic and the deterministic backward pass lsr_testutil.grad_check against
 the float oracle at its tolerances (per element 1e-4 |ref| + 1e-4 A for language, opacity and
@@ -25,9 +28,11 @@ and COL, deterministic, accumulate=True into buffers prefilled with a fixed nonz
 prefill + the accumulate=False result bit for bit in every row, and the rows of culled Gaussians
 (radii 0) keep the prefill bit for bit.
 
-Measured on an MI355X, maxima over the 7 cases (recorded, not used to set any bound): deterministic
-err / A language 2.8e-07, opacity 1.5e-07, means2D 2.2e-07, grad_err <= 1.8e-06 in every field;
-atomic err / A language 1.7e-05, opacity 4.7e-06, means2D 4.6e-06, grad_err <= 2.7e-05 (scales).
+Measured on an MI355X, maxima over the 8 cases (recorded, not used to set any bound): deterministic
+err / A language 3.7e-07 and opacity 2.2e-07 (both CLAMP), means2D 2.2e-07, grad_err <= 3.7e-06 in
+every field (language, COL); atomic err / A language 1.7e-05, opacity 4.7e-06, means2D 4.6e-06,
+grad_err <= 2.7e-05 (scales).  CLAMP alone: atomic grad_err means3D 2.0e-06, deterministic 4.1e-07,
+with means3D gradients of up to 117 on its frustum-clamped rows.
 """
 import numpy as np
 import pytest
@@ -62,7 +67,7 @@ def _setup(name):
 
 
 @pytest.mark.parametrize("deterministic", [False, True], ids=["atomic", "deterministic"])
-@pytest.mark.parametrize("name", list(bwd_cases.PP_CASES))
+@pytest.mark.parametrize("name", list(bwd_cases.PP_CASES) + ["CLAMP"])
 def test_one_view_branch(name, deterministic):
     c, ref, nat, ups = _setup(name)
     g = dgr.backward_native(nat[4], *ups, deterministic=deterministic)
