@@ -15,6 +15,7 @@
 //   below, on the same MFMA helpers.
 #include "lsr_common.h"
 #include "lsr_internal.h"
+#include "centers_kmeans.h"
 #include <algorithm>
 
 namespace lsr {
@@ -1177,6 +1178,90 @@ void launch_lang_deform_fwd(const LangDeformArgs& a, hipStream_t st) {
 }
 void launch_lang_deform_bwd(const LangDeformArgs& a, hipStream_t st) {
     if (a.P > 0) hipLaunchKernelGGL(k_lang_deform_bwd, dim3((a.P + DN - 1) / DN), dim3(256), 0, st, a);
+}
+
+// ==== status centres (include/lsr_centers.h): lang_deform at S times per Gaussian, then k-means ====
+// A block takes gpb Gaussians.  Their gpb * S rows (normalised language, time s of Gaussian g) go
+// through lang_mlp_fwd in tiles of 64 -- a tile spans Gaussians, so only the block's last tile has
+// idle rows -- and each normalised output row lands in s_x[row][D | 1], the samples.  A tile is handed
+// to lang_mlp_fwd as a 64-Gaussian problem of its own whose language rows and times sit in LDS (s_tl,
+// s_time): the MLP's code and arithmetic are k_lang_deform_fwd's.  Then wave w runs the k-means
+// (centers_kmeans.h) of Gaussians w, w + 4, ... on those rows.  The samples reach memory only when
+// samples_out is given.
+__device__ __forceinline__ float centers_time(uint32_t seed, uint32_t g, uint32_t s) {   // lsr_centers.h
+    uint32_t h = seed ^ (g * 0x9E3779B1u) ^ (s * 0x85EBCA77u);
+    h ^= h >> 16;
+    h *= 0x7FEB352Du;
+    h ^= h >> 15;
+    h *= 0x846CA68Bu;
+    h ^= h >> 16;
+    return (float)(h >> 8) * (1.0f / 16777216.0f);
+}
+
+constexpr int CF_MAX_GPB = 16;
+__global__ void __launch_bounds__(256) k_centers_from_field(CentersArgs ca) {
+    __shared__ __attribute__((aligned(16))) __bf16 s_xh[DN * DLP];
+    __shared__ __attribute__((aligned(16))) __bf16 s_xl[DN * DLP];
+    __shared__ __attribute__((aligned(16))) __bf16 s_hh[2][DN * DAP];
+    __shared__ __attribute__((aligned(16))) __bf16 s_hl[2][DN * DAP];
+    __shared__ float s_v[DN][33];
+    __shared__ float s_x[CK_XFLOATS];
+    __shared__ float s_lang[CF_MAX_GPB * 32];   // the block's normalised languages
+    __shared__ float s_tl[DN * CK_MAX_D];       // the tile's language rows [64][D]
+    __shared__ float s_time[DN];                // the tile's times
+    __shared__ float s_c[4][CK_MAX_K * CK_MAX_D];
+    __shared__ uint8_t s_a[4][CK_MAX_S];
+    LDS_POISON(s_xh); LDS_POISON(s_xl); LDS_POISON(s_hh); LDS_POISON(s_hl); LDS_POISON(s_v); LDS_POISON(s_x);
+    LDS_POISON(s_lang); LDS_POISON(s_tl); LDS_POISON(s_time); LDS_POISON(s_c); LDS_POISON(s_a); LDS_POISON_DONE();
+    const LangDeformArgs& a = ca.f;
+    const int tid = threadIdx.x, wave = tid >> 6, S = ca.S, D = a.lang_dim, xp = ck_pitch(D);
+    const int g0 = blockIdx.x * ca.gpb, ng = min(ca.gpb, a.P - g0), nrows = ng * S;
+    const int kpad = (a.kin + 15) / 16 * 16;
+    LangDeformArgs tile = a;
+    tile.lang = s_tl;
+    tile.time = s_time;
+    if (tid < ng) {   // l = lang / (|lang| + 1e-9)
+        const float* l = a.lang + (size_t)(g0 + tid) * D;
+        float n2 = 0.0f;
+        for (int c = 0; c < D; ++c) n2 += l[c] * l[c];
+        const float inv = 1.0f / (sqrtf(n2) + 1e-9f);
+        for (int c = 0; c < D; ++c) s_lang[tid * 32 + c] = l[c] * inv;
+    }
+    __syncthreads();
+    for (int r0 = 0; r0 < nrows; r0 += DN) {
+        tile.P = min(DN, nrows - r0);
+        for (int i = tid; i < tile.P * D; i += 256) s_tl[i] = s_lang[((r0 + i / D) / S) * 32 + i % D];
+        if (tid < DN && r0 + tid < nrows) {
+            const int lg = (r0 + tid) / S, s = (r0 + tid) - lg * S;
+            const size_t at = (size_t)(g0 + lg) * S + s;
+            const float t = ca.times ? ca.times[at] : centers_time(ca.seed, (uint32_t)(g0 + lg), (uint32_t)s);
+            s_time[tid] = t;
+            if (ca.times_out) ca.times_out[at] = t;
+        }
+        __syncthreads();   // the tile's rows and times; the previous tile's s_v read
+        lang_mlp_fwd(tile, 0, kpad, s_xh, s_xl, s_hh, s_hl, s_v, false);
+        if (tid < DN && r0 + tid < nrows) {   // x = v / (|v| + 1e-9), as k_lang_deform_fwd
+            float n2 = 0.0f;
+            for (int c = 0; c < D; ++c) n2 += s_v[tid][c] * s_v[tid][c];
+            const float inv = 1.0f / (sqrtf(n2) + 1e-9f);
+            float* xr = s_x + (r0 + tid) * xp;
+            for (int c = 0; c < D; ++c) xr[c] = s_v[tid][c] * inv;
+            if (ca.samples_out) {
+                float* o = ca.samples_out + ((size_t)g0 * S + r0 + tid) * D;
+                for (int c = 0; c < D; ++c) o[c] = xr[c];
+            }
+        }
+    }
+    __syncthreads();
+    for (int lg = wave; lg < ng; lg += 4) {
+        const size_t g = (size_t)(g0 + lg);
+        kmeans_wave(s_x + lg * S * xp, xp, S, D, ca.K, ca.max_iter, s_c[wave], s_a[wave], ca.centers + g * ca.K * D,
+                    ca.counts + g * ca.K, ca.inertia + g, ca.iters + g);
+    }
+}
+
+void launch_centers_from_field(const CentersArgs& a, hipStream_t st) {
+    if (a.f.P > 0) hipLaunchKernelGGL(k_centers_from_field, dim3((a.f.P + a.gpb - 1) / a.gpb), dim3(256), 0, st, a);
 }
 
 // ==== head weight gradients by recompute ===========================================================

@@ -326,6 +326,20 @@ BwdScratch bwd_scratch(const lsr_deform_net* net, size_t P) {
 
 }  // namespace
 
+namespace lsr {
+// centers.hip (include/lsr_centers.h): the lang_deform arguments of a checked, prepared net
+int deform_lang_args(const lsr_deform_net* net, const void* workspace, int32_t P, LangDeformArgs* out) {
+    int rc = check(net);
+    if (rc) return rc;
+    if (!lang_mlp(net))
+        return fail(LSR_EINVAL, "the centres are sampled from a field that deforms the language: lang_mode must be "
+                                "RESIDUAL or NORESNET");
+    if (!workspace) return fail(LSR_EINVAL, "the prepared workspace is required");
+    *out = lang_args(net, workspace, P);
+    return LSR_OK;
+}
+}  // namespace lsr
+
 extern "C" int lsr_deform_require_api(int32_t caller_version) {
     if (caller_version != LSR_DEFORM_API_VERSION)
         return lsr::fail(LSR_EINVAL, "lsr_deform.h version mismatch: caller " + std::to_string(caller_version) +

@@ -366,6 +366,23 @@ struct LangDeformArgs {
 void launch_lang_deform_fwd(const LangDeformArgs& a, hipStream_t st);
 void launch_lang_deform_bwd(const LangDeformArgs& a, hipStream_t st);
 
+// The status centres (include/lsr_centers.h), fused: a block takes `gpb` Gaussians, runs lang_deform
+// on their gpb * S (language, time) rows in tiles of 64 and the k-means of each Gaussian's S rows
+// (centers_kmeans.h) on the samples in LDS.  f.lang is the raw language [P, lang_dim]; f.time and
+// f.out_lang are unused.
+struct CentersArgs {
+    LangDeformArgs f;
+    const float* times;               // [P, S] or null: the generator of (seed, g, s)
+    uint32_t seed;
+    int S, K, max_iter, gpb;
+    float* centers;                   // [P, K, lang_dim]
+    int32_t* counts;                  // [P, K]
+    float* inertia;                   // [P]
+    int32_t* iters;                   // [P]
+    float *samples_out, *times_out;   // [P, S, lang_dim], [P, S] or null
+};
+void launch_centers_from_field(const CentersArgs& a, hipStream_t st);
+
 void launch_preprocess(const PreprocessArgs& a, hipStream_t st);
 void launch_reduce_lang(int P, int C, int cpad, int recq, const float* rec, const uint8_t* flags,
                         const uint32_t* inst_off, const uint32_t* tiles, float* dlang, bool accumulate, hipStream_t st);

@@ -118,6 +118,9 @@ PCA_BLOCK_PIXELS = 2048     # LSR_PCA_BLOCK_PIXELS
 PCA_TILE_PIXELS = 256       # LSR_PCA_TILE_PIXELS
 PCA_FINISH_WAVES = 16       # LSR_PCA_FINISH_WAVES
 PCA_RANGE_THREADS = 256     # LSR_PCA_RANGE_THREADS
+CENTERS_MAX_K = 8           # LSR_CENTERS_MAX_K (include/lsr_centers.h)
+CENTERS_MAX_SAMPLES = 256   # LSR_CENTERS_MAX_SAMPLES
+CENTERS_MAX_DIM = 32        # LSR_CENTERS_MAX_DIM
 
 _vp = ctypes.c_void_p
 SIGNATURES = {
@@ -271,6 +274,9 @@ SIGNATURES = {
                                        ctypes.c_int32, _vp, _vp, _vp, _vp]),
     "lsr_pca_colorize_f32": (ctypes.c_int, [ctypes.c_int64, _vp, _vp, _vp, _vp]),
     "lsr_pca_colorize_u8": (ctypes.c_int, [ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    "lsr_centers_kmeans": (ctypes.c_int, [_vp] + [ctypes.c_int32] * 5 + [_vp] * 5),
+    "lsr_centers_from_field": (ctypes.c_int, [ctypes.POINTER(DeformNet), _vp, ctypes.c_int32, _vp, _vp, ctypes.c_uint32]
+                               + [ctypes.c_int32] * 3 + [_vp] * 7),
     "lsr_profile_read": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
                                         ctypes.c_int32]),
 }
