@@ -372,6 +372,19 @@ class DeformationField:
         self._grad_flat.zero_()
         self.grads = dict(self._grad_views)
 
+    def regularize(self, weights, accumulate: bool = True):
+        """The HexPlane regularisers of this field's planes (plane_regularizer.regularize_planes; weights =
+        (time_smoothness_weight, l1_time_planes_weight, plane_tv_weight)): their gradient is added to
+        self.grads (or overwrites the planes' entries: accumulate=False), as backward() adds the render's.
+        Returns the PlaneReg (total, the terms)."""
+        from plane_regularizer import regularize_planes
+        if not hasattr(self, "grads"):
+            self.zero_grad()
+        S = range(len(self.multires))
+        planes = [[self.p[f"grid.grids.{s}.{ci}"] for ci in range(6)] for s in S]
+        grads = [[self.grads[f"grid.grids.{s}.{ci}"] for ci in range(6)] for s in S]
+        return regularize_planes(planes, weights, grads, accumulate)
+
     def backward(self, means3D, time, d_means3D, d_scales, d_rotations, d_opacity, d_shs, rotations=None, lang=None,
                  d_lang=None, d_coff=None, no_dlang: Optional[bool] = None):
         """Gradients of forward() given the gradients of its outputs: returns the input gradients

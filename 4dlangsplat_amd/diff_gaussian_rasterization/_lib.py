@@ -102,6 +102,12 @@ class Decoder(ctypes.Structure):
                 ("bias", ctypes.c_void_p * 8)]
 
 
+class PlaneDesc(ctypes.Structure):
+    """include/lsr_plane_reg.h lsr_plane_desc"""
+    _fields_ = [("t", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("C", ctypes.c_int32), ("H", ctypes.c_int32),
+                ("W", ctypes.c_int32), ("w_smooth", ctypes.c_double), ("w_l1", ctypes.c_double)]
+
+
 ADAM_MAX_GROUPS = 16        # LSR_ADAM_MAX_GROUPS
 GATHER_MAX_TENSORS = 32     # LSR_GATHER_MAX_TENSORS
 SEG_LOSS_MAX_VIEWS = 8      # lsr_seg_loss_views' V
@@ -121,6 +127,9 @@ PCA_RANGE_THREADS = 256     # LSR_PCA_RANGE_THREADS
 CENTERS_MAX_K = 8           # LSR_CENTERS_MAX_K (include/lsr_centers.h)
 CENTERS_MAX_SAMPLES = 256   # LSR_CENTERS_MAX_SAMPLES
 CENTERS_MAX_DIM = 32        # LSR_CENTERS_MAX_DIM
+PLANE_REG_API_VERSION = 1   # LSR_PLANE_REG_API_VERSION (include/lsr_plane_reg.h)
+PLANE_REG_MAX_PLANES = 24   # LSR_PLANE_REG_MAX_PLANES
+PLANE_REG_BLOCK_ELEMS = 1024  # LSR_PLANE_REG_BLOCK_ELEMS
 
 _vp = ctypes.c_void_p
 SIGNATURES = {
@@ -277,6 +286,8 @@ SIGNATURES = {
     "lsr_centers_kmeans": (ctypes.c_int, [_vp] + [ctypes.c_int32] * 5 + [_vp] * 5),
     "lsr_centers_from_field": (ctypes.c_int, [ctypes.POINTER(DeformNet), _vp, ctypes.c_int32, _vp, _vp, ctypes.c_uint32]
                                + [ctypes.c_int32] * 3 + [_vp] * 7),
+    "lsr_plane_reg_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.POINTER(PlaneDesc)]),
+    "lsr_plane_reg": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(PlaneDesc), ctypes.c_int32] + [_vp] * 5),
     "lsr_profile_read": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
                                         ctypes.c_int32]),
 }

@@ -167,7 +167,7 @@ def enter_discrete_stage(step, init_from_stage: str = "fine-base", centers: int 
     new = TrainStep(tr, discrete_field_from(field, centers, seed=int(field_seed)), bg=step.bg, stage="fine-lang-discrete",
                     sh_degree=step.sh_degree, densify=step.densify, batch_views=step.batch_views,
                     joint_train=step.joint_train, lam=step.lam, beta=step.beta, addcosloss=step.addcosloss,
-                    lambda_dssim=step.lambda_dssim)
+                    lambda_dssim=step.lambda_dssim, plane_reg=getattr(step, "plane_reg", None))
     deform_lr = next((lr for n, lr in step.field_opt.lr.items() if not n.startswith("grid.")), None)
     for n in new.field_opt.lr:   # the learning rates the old step ran with (the coff head takes the MLPs')
         if n in step.field_opt.lr:

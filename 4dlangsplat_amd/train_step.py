@@ -16,7 +16,9 @@ optimizer.step() skips its freshly built nn.Parameters; the deformation field st
 The deformation field's parameters get their own Adam (their groups in training_setup,
 scene/gaussian_model.py:273-276) and are repacked after every update.  Regularisers the reference
 adds nothing here: its TV / time-smoothness term is gated on `stage == "fine"` (train.py:331), which
-never equals the stage names it runs ('fine-base', 'fine-lang').  lambda_dssim defaults to 0
+never equals the stage names it runs ('fine-base', 'fine-lang'); TrainStep(plane_reg=...) adds that term
+(compute_regulation, scene/gaussian_model.py:763-802) where the gate was meant to fire, one fused call
+(plane_regularizer, DeformationField.regularize).  lambda_dssim defaults to 0
 (arguments/__init__.py:146), where the base-stage loss is the L1 alone; TrainStep(lambda_dssim=...) adds the
 reference's lambda_dssim * (1 - ssim(images, gts)) (train.py:335-337) in every stage, the L1 and the SSIM of the
 renders from one fused forward and one fused backward (image_loss.image_loss_views).
@@ -155,7 +157,7 @@ class TrainStep:
                  bg: Optional[torch.Tensor] = None, stage: str = "fine-base", sh_degree: int = 3,
                  densify: Optional[Callable[[GaussianTrainer, int], None]] = None, batch_views: bool = True,
                  joint_train: bool = False, lam: float = 0.2, beta: float = 0.01, addcosloss: bool = False,
-                 lambda_dssim: float = 0.0):
+                 lambda_dssim: float = 0.0, plane_reg: Optional[Sequence[float]] = None):
         """densify(trainer, iteration): optional densify / prune / reset_opacity schedule, run
         between the densification statistics and the optimizer step (train.py:388-421).
         batch_views: the batch's views share one deformation-field launch (render_views)
@@ -171,7 +173,14 @@ class TrainStep:
         lambda_dssim * (1 - ssim(renders, gts[:, :3])) as train.py:335-337 adds it in every stage: a constant
         in a 'lang' stage without joint_train, whose renders carry no gradient.  The reference passes its
         ground truth unsliced there, and with a 4-channel ground truth its grouped convolution raises;
-        gts[:, :3], the slice its L1 takes, is the only reading that runs."""
+        gts[:, :3], the slice its L1 takes, is the only reading that runs.
+        plane_reg: (time_smoothness_weight, l1_time_planes_weight, plane_tv_weight), or what
+        plane_regularizer.plane_reg_from_hidden gives.  None, the default and the reference's effective
+        behaviour (its gate `stage == "fine"`, train.py:331, never matches its stage names), leaves
+        forward_backward() on the path it had.  Otherwise compute_regulation's term (the HexPlane smoothness
+        and L1 regularisers, scene/gaussian_model.py:763-802) joins the loss where the lineage meant it: in
+        the 'fine' stages whose planes train ('fine-base', or a fine 'lang' stage with joint_train); in any
+        other stage it is skipped."""
         if joint_train and "lang" not in stage:
             raise ValueError("joint_train needs a 'lang' stage (train.py:103-104)")
         if "lang" in stage and "language_feature" not in trainer.params:
@@ -179,6 +188,14 @@ class TrainStep:
         self.trainer, self.field, self.stage = trainer, field, stage
         self.joint_train, self.lam, self.beta, self.addcosloss = joint_train, lam, beta, addcosloss
         self.lambda_dssim = float(lambda_dssim)
+        if plane_reg is not None:
+            if field is None:
+                raise ValueError("plane_reg regularises the deformation field's planes: a field is required")
+            plane_reg = tuple(float(w) for w in plane_reg)
+            if len(plane_reg) != 3:
+                raise ValueError("plane_reg = (time_smoothness_weight, l1_time_planes_weight, plane_tv_weight)")
+        self.plane_reg = plane_reg
+        self.plane_reg_terms = None  # the last iteration's plane_regularizer.PlaneReg, for logging
         self.coff = []              # the last iteration's renders' coff (train.py:240-247)
         self.batch_views = batch_views
         self.densify = densify
@@ -304,7 +321,24 @@ class TrainStep:
         self.coff = [o["coff"] for o in outs if o.get("coff") is not None]
         loss = self.loss(outs, gts, gt_lang, lang_mask, lang_sup)
         loss.backward()
+        if self.plane_reg is not None:
+            loss = self.add_plane_reg(loss)
         return loss, outs
+
+    @property
+    def plane_reg_active(self) -> bool:
+        """Whether plane_reg applies in this stage: a 'fine' stage whose planes train."""
+        return self.plane_reg is not None and "fine" in self.stage and self.field_trainable("grid.grids.0.0")
+
+    def add_plane_reg(self, loss: torch.Tensor) -> torch.Tensor:
+        """The plane regularisers' share of an iteration, after loss.backward(): their gradient added to
+        the field's plane gradients and their total to the loss (train.py:331-334); one fused call.  Where
+        plane_reg does not apply the loss comes back as it is and nothing is touched."""
+        if not self.plane_reg_active:
+            self.plane_reg_terms = None
+            return loss
+        self.plane_reg_terms = self.field.regularize(self.plane_reg, accumulate=True)
+        return loss.detach() + self.plane_reg_terms.total
 
     def __call__(self, cams: Sequence, gts: Optional[torch.Tensor], iteration: Optional[int] = None,
                  gt_lang: Optional[torch.Tensor] = None, lang_mask: Optional[torch.Tensor] = None,

@@ -13,7 +13,8 @@ pieces, densification on the reference schedule.
   iteration    train.py:224-421 via train_step.TrainStep: `views` random cameras of the pool, render,
                L1 (the base-stage loss: train.py:287, 331-337), backward, densification statistics,
                ReferenceSchedule (train.py:388-414 with the Neu3D overrides), Adam on the Gaussians and
-               the field, the reference's learning-rate schedules (gaussian_model.py:302-330)
+               the field, the reference's learning-rate schedules (gaussian_model.py:302-330);
+               --plane-reg adds the HexPlane regularisers (train.py:331-334, off by default)
 
 Prints one JSON line: iterations/s over the whole loop (densify / prune included), the mean loss per
 window of `window` iterations (the loss must fall window over window), the densify / prune events,
@@ -117,6 +118,10 @@ def build(args, dev):
     sched = ReferenceSchedule(extent, stage="fine-base", densify_until_iter=args.densify_until_iter)
     step = TrainStep(tr, field, densify=sched, stage="fine-base")
     step.set_reference_lr(extent)
+    mode = getattr(args, "plane_reg", "off")
+    if mode != "off":
+        import bench_plane_reg
+        bench_plane_reg.set_plane_reg(step, mode)
     return step, sched, pool, gts, extent
 
 
@@ -177,6 +182,11 @@ def main():
     ap.add_argument("--per-view-deform", action="store_true",
                     help="one deformation launch per view (render) instead of one per iteration over all views "
                          "(render_views, TrainStep's default)")
+    ap.add_argument("--plane-reg", choices=("off", "fused", "torch"), default="off",
+                    help="the HexPlane regularisers with the Neu3D weights (arguments/neu3d/default.py:11-13): off "
+                         "(the reference's effective behaviour), the fused call (TrainStep(plane_reg=...)), or the "
+                         "same term as torch ops.  Compare the three from runs made in turn in one session "
+                         "(tools/bench_plane_reg.py --loop alternates them in one process)")
     args = ap.parse_args()
     dev = torch.device("cuda")
     torch.manual_seed(0)
@@ -226,7 +236,8 @@ def main():
                 config=dict(workload="configs[4] stand-in: synthetic teacher, Neu3D field, fine-base",
                             gaussians=args.gaussians, views_per_iteration=args.views, width=args.width,
                             height=args.height, pool=len(pool), resolution=NEU3D_RES, multires=NEU3D_MULTIRES,
-                            deformation_launches="per view" if args.per_view_deform else "one per iteration"),
+                            deformation_launches="per view" if args.per_view_deform else "one per iteration",
+                            plane_reg=args.plane_reg),
                 data="synthetic")
     print(json.dumps(line))
 
