@@ -16,6 +16,7 @@ c_float_p = ctypes.c_void_p  # device pointers are passed as opaque addresses
 API_VERSION = 4               # LSR_API_VERSION of the include/lsr.h these structs mirror
 DEFORM_API_VERSION = 3        # LSR_DEFORM_API_VERSION of include/lsr_deform.h (DeformNet, DeformGrads)
 QUERY_API_VERSION = 1         # LSR_QUERY_API_VERSION of include/lsr_query.h (Decoder)
+VIDEO_API_VERSION = 1         # LSR_VIDEO_API_VERSION of include/lsr_video.h
 
 
 class Settings(ctypes.Structure):
@@ -130,6 +131,10 @@ CENTERS_MAX_DIM = 32        # LSR_CENTERS_MAX_DIM
 PLANE_REG_API_VERSION = 1   # LSR_PLANE_REG_API_VERSION (include/lsr_plane_reg.h)
 PLANE_REG_MAX_PLANES = 24   # LSR_PLANE_REG_MAX_PLANES
 PLANE_REG_BLOCK_ELEMS = 1024  # LSR_PLANE_REG_BLOCK_ELEMS
+VIDEO_MAX_WIDTH = 4096      # LSR_VIDEO_MAX_WIDTH (include/lsr_video.h)
+VIDEO_MAX_QUERIES = 16      # LSR_VIDEO_MAX_QUERIES
+VIDEO_ROW_TILE = 128        # LSR_VIDEO_ROW_TILE
+VIDEO_COL_TILE = 128        # LSR_VIDEO_COL_TILE
 
 _vp = ctypes.c_void_p
 SIGNATURES = {
@@ -288,6 +293,11 @@ SIGNATURES = {
                                + [ctypes.c_int32] * 3 + [_vp] * 7),
     "lsr_plane_reg_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.POINTER(PlaneDesc)]),
     "lsr_plane_reg": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(PlaneDesc), ctypes.c_int32] + [_vp] * 5),
+    "lsr_video_require_api": (ctypes.c_int, [ctypes.c_int32]),
+    "lsr_video_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(Decoder), ctypes.c_int64]),
+    "lsr_video_cosine": (ctypes.c_int, [ctypes.POINTER(Decoder), ctypes.c_int64, _vp, ctypes.c_int32, _vp, _vp, _vp,
+                                        ctypes.c_int64, _vp]),
+    "lsr_video_segment_mean": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp]),
     "lsr_profile_read": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
                                         ctypes.c_int32]),
 }
@@ -328,7 +338,8 @@ def load():
             fn.restype = res
             fn.argtypes = args
         if (lib.lsr_require_api(API_VERSION) != 0 or lib.lsr_deform_require_api(DEFORM_API_VERSION) != 0
-                or lib.lsr_query_require_api(QUERY_API_VERSION) != 0):
+                or lib.lsr_query_require_api(QUERY_API_VERSION) != 0
+                or lib.lsr_video_require_api(VIDEO_API_VERSION) != 0):
             raise ImportError(f"{path}: {lib.lsr_last_error().decode()} (rebuild it: make -C 4dlangsplat_amd/csrc)")
         _LIB = lib
     return _LIB
