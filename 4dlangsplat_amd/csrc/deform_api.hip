@@ -8,6 +8,7 @@
 #include "../../include/lsr.h"
 #include "../../include/lsr_deform.h"
 #include "lsr_internal.h"
+#include "deform_narrow.h"
 #include <vector>
 
 static_assert(lsr::DEF_UNPACK_MAX == 6 * LSR_DEFORM_MAX_SCALES, "one unpack slot per plane");
@@ -105,8 +106,16 @@ int check(const lsr_deform_net* n) {
         return lsr::fail(LSR_EINVAL, "call lsr_deform_require_api(LSR_DEFORM_API_VERSION) first: the caller must be "
                                      "built against lsr_deform.h version " + std::to_string(LSR_DEFORM_API_VERSION));
     if (!n) return lsr::fail(LSR_EINVAL, "null deformation net");
-    if (n->n_scales < 1 || n->n_scales > LSR_DEFORM_MAX_SCALES || n->channels != 16 || n->width != kW)
-        return lsr::fail(LSR_EINVAL, "supported: 1..4 scales x 16 channels, width 128 (every HyperNeRF / Neu3D config)");
+    const bool narrow = lsr::deform_is_narrow(n);
+    if (n->n_scales < 1 || n->n_scales > LSR_DEFORM_MAX_SCALES || ((n->channels != 16 || n->width != kW) && !narrow))
+        return lsr::fail(LSR_EINVAL, "supported: 1..4 scales x 16 channels, width 128 (every HyperNeRF / Neu3D config) "
+                                     "or x 32 channels, width 64 (D-NeRF, the ModelHiddenParams defaults)");
+    if (narrow && n->lang_mode >= LSR_DEFORM_LANG_PASS && n->lang_mode <= LSR_DEFORM_LANG_DISCRETE &&
+        n->lang_mode != LSR_DEFORM_LANG_PASS) {
+        static const char* const kMode[] = {"PASS", "RESIDUAL", "NORESNET", "DISCRETE"};
+        return lsr::fail(LSR_EINVAL, std::string("language mode ") + kMode[n->lang_mode] +
+                                         " is not supported at 32 channels / width 64 (PASS only)");
+    }
     if (n->depth < 0 || n->depth > LSR_DEFORM_MAX_DEPTH) return lsr::fail(LSR_EINVAL, "defor_depth must be in [0, 4]");
     for (int c = 0; c < 4; ++c)
         if (n->res[c] < 2) return lsr::fail(LSR_EINVAL, "plane resolutions must be >= 2");
@@ -142,6 +151,7 @@ int check(const lsr_deform_net* n) {
 
 extern "C" int64_t lsr_deform_workspace_bytes(const lsr_deform_net* net) {
     if (check(net)) return -1;
+    if (lsr::deform_is_narrow(net)) return lsr::narrow_workspace_bytes(net);
     return (int64_t)layout(net).total;
 }
 
@@ -150,6 +160,11 @@ extern "C" int lsr_deform_prepare(const lsr_deform_net* net, void* workspace, vo
     if (rc) return rc;
     if (!workspace) return lsr::fail(LSR_EINVAL, "workspace is required");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (lsr::deform_is_narrow(net)) {
+        lsr::narrow_prepare(net, workspace, st);
+        if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "deformation packing launch failed");
+        return LSR_OK;
+    }
     const Layout L = layout(net);
     char* ws = reinterpret_cast<char*>(workspace);
     std::vector<lsr::PackJob> jobs;   // every packing job, then one launch (lsr::launch_pack_batch)
@@ -331,6 +346,8 @@ namespace lsr {
 int deform_lang_args(const lsr_deform_net* net, const void* workspace, int32_t P, LangDeformArgs* out) {
     int rc = check(net);
     if (rc) return rc;
+    if (deform_is_narrow(net))   // its workspace has another layout (deform_narrow.hip) and no lang_deform
+        return fail(LSR_EINVAL, "the centres are not supported for a field of 32 channels / width 64");
     if (!lang_mlp(net))
         return fail(LSR_EINVAL, "the centres are sampled from a field that deforms the language: lang_mode must be "
                                 "RESIDUAL or NORESNET");
@@ -366,6 +383,11 @@ extern "C" int lsr_deform_forward(const lsr_deform_net* net, const void* workspa
     if (net->lang_mode != LSR_DEFORM_LANG_PASS && (!lang || !out_lang))
         return lsr::fail(LSR_EINVAL, "lang and out_lang are required unless the language passes through");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (lsr::deform_is_narrow(net)) {
+        lsr::narrow_forward(net, workspace, P, means3D, time, ins, outs, st);
+        if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "deformation forward launch failed");
+        return LSR_OK;
+    }
     lsr::DeformArgs a = forward_args(net, workspace, P);
     a.means3D = means3D;
     a.time = time;
@@ -390,6 +412,7 @@ extern "C" int lsr_deform_forward(const lsr_deform_net* net, const void* workspa
 
 extern "C" int64_t lsr_deform_backward_scratch_bytes(const lsr_deform_net* net, int32_t P) {
     if (check(net) || P < 0) return -1;
+    if (lsr::deform_is_narrow(net)) return lsr::narrow_backward_scratch_bytes(net, P);
     return (int64_t)bwd_scratch(net, (size_t)(P > 0 ? P : 1)).total;
 }
 
@@ -425,6 +448,13 @@ extern "C" int lsr_deform_backward(const lsr_deform_net* net, const void* worksp
         for (int ci = 0; ci < 6; ++ci)
             if (!grads->planes[s][ci]) return lsr::fail(LSR_EINVAL, "missing plane gradient");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (lsr::deform_is_narrow(net)) {
+        if (lsr::narrow_backward(net, workspace, P, means3D, rotations, time, ups, d_means3D, d_rotations, grads, scratch,
+                                 st) != hipSuccess)
+            return lsr::fail(LSR_EHIP, "memset");
+        if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "deformation backward launch failed");
+        return LSR_OK;
+    }
     const Layout L = layout(net);
     const BwdScratch S = bwd_scratch(net, (size_t)P);
     char* sc = reinterpret_cast<char*>(scratch);

@@ -1,5 +1,6 @@
 """The 4D deformation field on MI355X: HexPlane sampling + MLP heads, fused in HIP kernels
-(csrc/deform.hip, C-ABI include/lsr_deform.h).  SURVEY.md 8(a) rows a2-a3, 8(f) row 1.
+(csrc/deform.hip; csrc/deform_narrow.hip for 32 plane channels and a 64-wide MLP; C-ABI
+include/lsr_deform.h).  SURVEY.md 8(a) rows a2-a3, 8(f) row 1.
 
 Mirrors the reference's `deform_network.forward_dynamic` (scene/deformation.py:232-248) with every
 switch its configs and scripts use: per Gaussian, HexPlane features at (xyz, t) -> feature_out
@@ -29,6 +30,21 @@ HEAD_OUT = (3, 3, 4, 1, 48)
 COFF = "discrete_coff_generator"
 LANG_PASS, LANG_RESIDUAL, LANG_NORESNET, LANG_DISCRETE = 0, 1, 2, 3   # include/lsr_deform.h
 MAX_DEPTH = 4
+#: (plane channels per scale, MLP width) pairs with native kernels: 16 / 128 (every HyperNeRF / Neu3D
+#: config, csrc/deform.hip) and 32 / 64 (D-NeRF and the ModelHiddenParams defaults, csrc/deform_narrow.hip)
+SHAPES = ((16, 128), (32, 64))
+_MODE_NAMES = {LANG_PASS: "PASS", LANG_RESIDUAL: "RESIDUAL", LANG_NORESNET: "NORESNET", LANG_DISCRETE: "DISCRETE"}
+
+
+def _check_shape_pair(channels: int, width: int, lang_mode: int):
+    """The (output_coordinate_dim, net_width) pair has kernels, and they run this language mode."""
+    if (channels, width) not in SHAPES:
+        raise ValueError(f"output_coordinate_dim {channels}, net_width {width}: supported: net_width 128, "
+                         "output_coordinate_dim 16 (every HyperNeRF / Neu3D config) or net_width 64, "
+                         "output_coordinate_dim 32 (D-NeRF, the ModelHiddenParams defaults)")
+    if (channels, width) == (32, 64) and lang_mode != LANG_PASS:
+        raise ValueError(f"language mode {_MODE_NAMES.get(lang_mode, lang_mode)} is not supported at "
+                         "output_coordinate_dim 32 / net_width 64 (PASS, no_dlang = 1, only)")
 # modules the reference always builds (scene/deformation.py:45-69, :208-215) whether or not the
 # configuration computes them
 _ALWAYS_BUILT = re.compile(r"^(timenet\.|time_poc$|pos_poc$|rotation_scaling_poc$|opacity_poc$|"
@@ -39,7 +55,8 @@ _ALWAYS_BUILT = re.compile(r"^(timenet\.|time_poc$|pos_poc$|rotation_scaling_poc
 class DeformationField:
     """params: name -> tensor, names as in the reference `Deformation` module (grid.grids.{s}.{ci},
     grid.aabb, feature_out.{2k}.*, {head}.1.* / .3.*, discrete_coff_generator.*, lang_deform.*) --
-    exactly the ones the configuration computes (anything else raises).
+    exactly the ones the configuration computes (anything else raises).  The network shape is read
+    from them (`channels`, `width`: 16 / 128 or 32 / 64, SHAPES; the latter with lang_mode LANG_PASS).
     resolution / multires: the kplanes_config resolution [x, y, z, t] and the multires list;
     depth: defor_depth; no_dx .. no_dshs, apply_rotation: ModelHiddenParams; lang_mode: LANG_*
     (no_dlang / use_discrete_lang_f / no_resnet), lang_dim: language_feature_hiddendim, centers:
@@ -68,6 +85,11 @@ class DeformationField:
             raise ValueError(f"deformation parameters do not match the configuration: unexpected {extra}, "
                              f"missing {missing}")
         self.p = {k: v.detach().to(self.device, torch.float32).contiguous() for k, v in params.items()}
+        # the network shape is the parameters' own: feature_out.0.weight is [width, channels S], a plane
+        # [1, channels, H, W]
+        self.width = int(self.p["feature_out.0.weight"].shape[0])
+        self.channels = int(self.p["grid.grids.0.0"].shape[1]) if self.p["grid.grids.0.0"].dim() == 4 else -1
+        _check_shape_pair(self.channels, self.width, self.lang_mode)
         self._check_shapes()
         self.net = self._net(self.lang_mode)
         L = _lib.load()
@@ -102,15 +124,15 @@ class DeformationField:
         return n
 
     def _check_shapes(self):
-        S, W = len(self.multires), 128
+        S, W, C = len(self.multires), self.width, self.channels
         exp = {}
         for s, m in enumerate(self.multires):
             reso = [r * m for r in self.resolution[:3]] + [self.resolution[3]]
             for ci, (c0, c1) in enumerate([(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)]):
-                exp[f"grid.grids.{s}.{ci}"] = (1, 16, reso[c1], reso[c0])
+                exp[f"grid.grids.{s}.{ci}"] = (1, C, reso[c1], reso[c0])
         exp["grid.aabb"] = (2, 3)
         for k in range(self.n_layers):
-            exp[f"feature_out.{2 * k}.weight"] = (W, 16 * S if k == 0 else W)
+            exp[f"feature_out.{2 * k}.weight"] = (W, C * S if k == 0 else W)
             exp[f"feature_out.{2 * k}.bias"] = (W,)
         outs = dict(zip(HEADS, HEAD_OUT), **{COFF: self.centers})
         for h in self.heads_computed():
@@ -128,7 +150,7 @@ class DeformationField:
     def _net(self, lang_mode, coff_head: Optional[bool] = None):
         coff_head = self.discrete if coff_head is None else coff_head
         n = _lib.DeformNet()
-        n.n_scales, n.channels, n.width = len(self.multires), 16, 128
+        n.n_scales, n.channels, n.width = len(self.multires), self.channels, self.width
         for i in range(4):
             n.res[i] = int(self.resolution[i])
             n.multires[i] = int(self.multires[i]) if i < len(self.multires) else 1
@@ -226,8 +248,10 @@ class DeformationField:
             raise ValueError("use_tribute_dlang is not supported (the reference's lang_deform input width "
                              "does not admit it)")
         kp = get("kplanes_config")
-        if get("net_width", 64) != 128 or kp.get("output_coordinate_dim", 32) != 16:
-            raise ValueError("supported: net_width 128, output_coordinate_dim 16 (every HyperNeRF / Neu3D config)")
+        if kp is None:   # the ModelHiddenParams default (arguments/__init__.py:88-93)
+            kp = {"grid_dimensions": 2, "input_coordinate_dim": 4, "output_coordinate_dim": 32,
+                  "resolution": [64, 64, 64, 25]}
+        width, channels = int(get("net_width", 64)), int(kp.get("output_coordinate_dim", 32))
         lang_dim = int(env.get("language_feature_hiddendim", 3))
         if env.get("use_discrete_lang_f", "f") == "t":
             mode = LANG_DISCRETE
@@ -235,6 +259,7 @@ class DeformationField:
             mode = LANG_PASS
         else:
             mode = LANG_NORESNET if env.get("no_resnet", "f") == "t" else LANG_RESIDUAL
+        _check_shape_pair(channels, width, mode)
         cfg = dict(resolution=list(kp["resolution"]), multires=list(get("multires", [1, 2, 4, 8])),
                    depth=int(get("defor_depth", 1)), no_dx=bool(get("no_dx", False)), no_ds=bool(get("no_ds", False)),
                    no_dr=bool(get("no_dr", False)), no_do=bool(get("no_do", True)), no_dshs=bool(get("no_dshs", True)),
@@ -258,6 +283,13 @@ class DeformationField:
             elif not _ALWAYS_BUILT.match(name):
                 raise ValueError(f"state-dict key {k!r} is not computed by this configuration "
                                  f"(defor_depth {cfg['depth']}, multires {cfg['multires']})")
+        # the tensors have the declared sizes (the constructor infers the shape from them)
+        w0, g0 = params.get("feature_out.0.weight"), params.get("grid.grids.0.0")
+        if w0 is not None and (w0.dim() != 2 or w0.shape[0] != width or w0.shape[1] != channels * len(cfg["multires"])):
+            raise ValueError(f"feature_out.0.weight: shape {tuple(w0.shape)}, but net_width {width} and "
+                             f"output_coordinate_dim {channels} x {len(cfg['multires'])} scales are declared")
+        if g0 is not None and (g0.dim() != 4 or g0.shape[1] != channels):
+            raise ValueError(f"grid.grids.0.0: shape {tuple(g0.shape)}, but output_coordinate_dim {channels} is declared")
         return params, cfg
 
     @classmethod
@@ -275,9 +307,9 @@ class DeformationField:
 
     def hidden_params(self) -> dict:
         """The ModelHiddenParams entries this field was built from (config_from_reference's input)."""
-        return dict(kplanes_config={"resolution": list(self.resolution), "output_coordinate_dim": 16,
+        return dict(kplanes_config={"resolution": list(self.resolution), "output_coordinate_dim": self.channels,
                                     "grid_dimensions": 2, "input_coordinate_dim": 4},
-                    multires=list(self.multires), defor_depth=self.depth, net_width=128,
+                    multires=list(self.multires), defor_depth=self.depth, net_width=self.width,
                     no_dx=not self.head_on[0], no_ds=not self.head_on[1], no_dr=not self.head_on[2],
                     no_do=not self.head_on[3], no_dshs=not self.head_on[4], apply_rotation=self.apply_rotation,
                     no_dlang=int(self.lang_mode == LANG_PASS), timebase_pe=self.time_pe)

@@ -63,6 +63,13 @@ def kmeans_rows(x: torch.Tensor, k: int, max_iter: int = 100):
     return centers, counts, inertia, iters
 
 
+def _refuse_narrow(field, what):
+    """The centres and the discrete stage exist for the 16-channel / 128-wide field only."""
+    if (getattr(field, "channels", 16), getattr(field, "width", 128)) != (16, 128):
+        raise ValueError(f"{what}: not supported for a field of output_coordinate_dim {field.channels} / "
+                         f"net_width {field.width} (it passes the language through; 16 / 128 only)")
+
+
 @torch.no_grad()
 def sample_centers(field: DeformationField, lang: torch.Tensor, k: int = 3, samples: int = 100, seed: int = 0,
                    times: Optional[torch.Tensor] = None, max_iter: int = 100, debug: bool = False):
@@ -71,6 +78,7 @@ def sample_centers(field: DeformationField, lang: torch.Tensor, k: int = 3, samp
     [P, samples], or the stateless generator of (seed, Gaussian, sample) -- and clustered per Gaussian.
     Returns (centers [P, k, D], counts, inertia, iters); with debug=True also the samples [P, S, D]
     and the times [P, S]."""
+    _refuse_narrow(field, "sample_centers")
     lang = _device_f32(lang, "lang")
     if lang.dim() != 2 or lang.shape[1] != field.lang_dim:
         raise ValueError(f"lang: [P, {field.lang_dim}]")
@@ -143,6 +151,7 @@ def enter_discrete_stage(step, init_from_stage: str = "fine-base", centers: int 
     old, field = step.trainer, step.field
     if field is None:
         raise ValueError("the discrete stage needs the step's deformation field")
+    _refuse_narrow(field, "enter_discrete_stage")
     if "language_feature" not in old.params:
         raise ValueError("the step has no language_feature group")
     lang = old.params["language_feature"].detach()

@@ -23,8 +23,13 @@
  *   NORESNET  normalize(lang_deform(...))                                    (:176-177)
  *   DISCRETE  the input holds `centers` centres of lang_dim channels; each is normalised, combined
  *             with coff = discrete_coff_generator(hidden), and the sum normalised   (:156-163)
+ * Network shapes (channels, width): (16, 128), every HyperNeRF / Neu3D / dycheck config, with every
+ * language mode; and (32, 64), the D-NeRF configs and the ModelHiddenParams defaults (arguments/
+ * __init__.py:84-113), with 1..4 scales, depth 0..4, every mask of the five geometry heads,
+ * apply_rotation and the PASS language mode.
  * Not supported (rejected): no_grid, grid_pe > 0, static_mlp, empty_voxel, use_tribute_dlang (off
- * in every reference config), channels != 16, width != 128.
+ * in every reference config), any other (channels, width) pair, and at (32, 64) the RESIDUAL /
+ * NORESNET / DISCRETE language modes and the status centres (lsr_centers.h).
  *
  * Conventions: device pointers, float32, contiguous, torch layouts (planes [1, C, res[c1],
  * res[c0]] for the coordinate pair (c0, c1) in the order xy, xz, xt, yz, yt, zt; Linear weights
@@ -48,8 +53,8 @@ extern "C" {
 
 typedef struct lsr_deform_net {
     int32_t n_scales;                   /* multires levels (Neu3D: 2, HyperNeRF: 3) */
-    int32_t channels;                   /* plane channels per scale (output_coordinate_dim); 16 */
-    int32_t width;                      /* MLP width (net_width); 128 */
+    int32_t channels;                   /* plane channels per scale (output_coordinate_dim): 16, or 32 with width 64 */
+    int32_t width;                      /* MLP width (net_width): 128, or 64 with 32 channels */
     int32_t res[4];                     /* base plane resolution x, y, z, t */
     int32_t multires[LSR_DEFORM_MAX_SCALES];   /* spatial multiplier of each scale (time unscaled) */
     int32_t depth;                      /* defor_depth: feature_out has max(depth, 1) Linear layers */
@@ -74,7 +79,8 @@ typedef struct lsr_deform_net {
  * (LSR_EINVAL, every entry point) instead of having its structs misread. */
 int lsr_deform_require_api(int32_t caller_version);
 
-/* Workspace holding the packed planes (channel-last) and weights (bf16 hi/lo).  -1: bad net. */
+/* Workspace holding the packed planes (channel-last) and weights (bf16 hi/lo; at 32 channels / width
+ * 64: fp32, transposed).  Its layout belongs to the net's shape.  -1: bad net. */
 int64_t lsr_deform_workspace_bytes(const lsr_deform_net *net);
 /* Pack the parameters into the workspace; call again after every parameter update. */
 int lsr_deform_prepare(const lsr_deform_net *net, void *workspace, void *stream);
