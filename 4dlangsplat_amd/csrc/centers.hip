@@ -1,6 +1,6 @@
 // centers.hip -- C ABI of the status centres (include/lsr_centers.h) and the k-means of rows that
 // are already in memory.  The fused kernel (time sampling through lang_deform, then the same k-means)
-// lives beside the language MLP in deform.hip (launch_centers_from_field).
+// lives beside the language MLP in deform_lang.hip (launch_centers_from_field).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,7 +9,7 @@
 #include "../../include/lsr.h"
 #include "../../include/lsr_centers.h"
 #include "centers_kmeans.h"
-#include "lsr_internal.h"
+#include "deform_internal.h"
 
 static_assert(lsr::CK_MAX_K == LSR_CENTERS_MAX_K && lsr::CK_MAX_S == LSR_CENTERS_MAX_SAMPLES &&
                   lsr::CK_MAX_D == LSR_CENTERS_MAX_DIM, "the kernel's limits are the header's");

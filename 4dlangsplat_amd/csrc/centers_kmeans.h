@@ -1,6 +1,6 @@
 // centers_kmeans.h -- the per-row k-means of include/lsr_centers.h as the work of ONE wave on samples
 // that sit in LDS.  Both entry points run this function (centers.hip on rows read from memory,
-// deform.hip on rows the language MLP has just produced), so their results are the same bits.
+// deform_lang.hip on rows the language MLP has just produced), so their results are the same bits.
 //
 // Lane l owns samples l, l + 64, ... (at most 4: S <= 256): distances, the argmax of the seeding and the
 // argmin of the assignment are per lane, folded over the wave by shuffles with (value, index) ties to

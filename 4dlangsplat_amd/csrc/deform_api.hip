@@ -7,7 +7,7 @@
 
 #include "../../include/lsr.h"
 #include "../../include/lsr_deform.h"
-#include "lsr_internal.h"
+#include "deform_host.h"
 #include "deform_narrow.h"
 #include <vector>
 
@@ -19,14 +19,11 @@ int fail(int code, const std::string& msg);   // lsr_api.hip (thread-local lsr_l
 
 namespace {
 
-constexpr int kCombos[6][2] = {{0, 1}, {0, 2}, {0, 3}, {1, 2}, {1, 3}, {2, 3}};
-constexpr int kHeadOut[5] = {3, 3, 4, 1, 48};
+using namespace lsr::deform_host;   // plane sizes and layout, layers, heads: shared with the 32 / 64 shape
+
 constexpr int kW = 128;   // MLP width
 
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-int nlayers(const lsr_deform_net* n) { return std::max(n->depth, 1); }
 int head_out(const lsr_deform_net* n, int hd) { return hd < 5 ? kHeadOut[hd] : n->centers; }
-bool head_on(const lsr_deform_net* n, int hd) { return (n->heads >> hd) & 1u; }
 int feat_dim(const lsr_deform_net* n) { return 16 * n->n_scales; }
 int lang_kin(const lsr_deform_net* n) { return n->lang_dim + 1 + 2 * n->time_pe; }
 int lang_kpad(const lsr_deform_net* n) { return (lang_kin(n) + 15) / 16 * 16; }
@@ -37,20 +34,12 @@ int lang_in(const lsr_deform_net* n) {
     return n->lang_mode == LSR_DEFORM_LANG_DISCRETE ? n->lang_dim * n->centers : n->lang_dim;
 }
 
-// plane 6 s + ci: width (along coordinate c0) and height (along c1)
-void plane_dims(const lsr_deform_net* n, int s, int ci, int& W, int& H) {
-    auto res = [&](int c) { return c < 3 ? n->res[c] * n->multires[s] : n->res[3]; };
-    W = res(kCombos[ci][0]);
-    H = res(kCombos[ci][1]);
-}
-
 // one packed bf16 hi / lo pair of `count` elements
 struct Pack {
     size_t off = 0, count = 0;
 };
 struct Layout {
-    size_t plane_off[24];   // bytes
-    size_t planes_end;      // bytes of the packed planes
+    PlaneLayout planes;     // channel-last [H][W][16]
     Pack wf[LSR_DEFORM_MAX_DEPTH], wft[LSR_DEFORM_MAX_DEPTH];
     Pack w1[LSR_DEFORM_HEADS], w2[LSR_DEFORM_HEADS], w1t[LSR_DEFORM_HEADS], w2t[LSR_DEFORM_HEADS];
     Pack wl[3], wlt[3];
@@ -59,15 +48,8 @@ struct Layout {
 
 Layout layout(const lsr_deform_net* n) {
     Layout L{};
-    size_t o = 0;
-    for (int s = 0; s < n->n_scales; ++s)
-        for (int ci = 0; ci < 6; ++ci) {
-            int W, H;
-            plane_dims(n, s, ci, W, H);
-            L.plane_off[6 * s + ci] = o;
-            o += align256((size_t)W * H * 16 * sizeof(float));
-        }
-    L.planes_end = o;
+    L.planes = plane_layout(n, 16);
+    size_t o = L.planes.end;
     auto take = [&](Pack& p, size_t count) {
         p.off = o;
         p.count = count;
@@ -182,7 +164,7 @@ extern "C" int lsr_deform_prepare(const lsr_deform_net* net, void* workspace, vo
         for (int ci = 0; ci < 6; ++ci) {
             int W, H;
             plane_dims(net, s, ci, W, H);
-            plane(net->planes[s][ci], reinterpret_cast<float*>(ws + L.plane_off[6 * s + ci]), H, W);
+            plane(net->planes[s][ci], reinterpret_cast<float*>(ws + L.planes.off[6 * s + ci]), H, W);
         }
     auto hi = [&](const Pack& p) { return reinterpret_cast<__bf16*>(ws + p.off); };
     auto lo = [&](const Pack& p) { return reinterpret_cast<__bf16*>(ws + p.off + align256(p.count * sizeof(__bf16))); };
@@ -240,14 +222,7 @@ lsr::DeformArgs forward_args(const lsr_deform_net* net, const void* workspace, i
     a.lang_in = lang_in(net);
     a.aabb = net->aabb;
     a.planes = reinterpret_cast<const float*>(ws);
-    for (int s = 0; s < net->n_scales; ++s)
-        for (int ci = 0; ci < 6; ++ci) {
-            int W, H;
-            plane_dims(net, s, ci, W, H);
-            a.poff[6 * s + ci] = (int64_t)(L.plane_off[6 * s + ci] / sizeof(float));
-            a.pw[6 * s + ci] = W;
-            a.ph[6 * s + ci] = H;
-        }
+    plane_args(net, L.planes, a.poff, a.pw, a.ph);
     for (int k = 0; k < a.nlayers; ++k) {
         a.wf_h[k] = chi<__bf16>(ws, L.wf[k]);
         a.wf_l[k] = clo<__bf16>(ws, L.wf[k]);
@@ -332,7 +307,7 @@ BwdScratch bwd_scratch(const lsr_deform_net* net, size_t P) {
     }
     s.daabb = take(lsr::DEF_AABB_SLOTS * 16);   // zeroed with the gradient planes (contiguous)
     s.dplanes = o;
-    o += (size_t)kGradReplicas * layout(net).planes_end;
+    o += (size_t)kGradReplicas * layout(net).planes.end;
     s.trow = o;                                                  // zeroed with the planes (contiguous)
     o += align256((size_t)kTimeRowReps * time_row_floats(net, nullptr) * f);
     s.total = o;
@@ -489,7 +464,7 @@ extern "C" int lsr_deform_backward(const lsr_deform_net* net, const void* worksp
     b.daabb = grads->aabb;
     b.daabb_part = fp(S.daabb);
     b.replicas = kGradReplicas;
-    b.plane_stride = (int64_t)(L.planes_end / sizeof(float));
+    b.plane_stride = (int64_t)(L.planes.end / sizeof(float));
     b.trow_reps = kTimeRowReps;
     b.trow = fp(S.trow);
     b.trow_stride = (int64_t)time_row_floats(net, b.toff);
@@ -549,19 +524,9 @@ extern "C" int lsr_deform_backward(const lsr_deform_net* net, const void* worksp
     u.trow_reps = b.trow_reps;
     u.trow_stride = b.trow_stride;
     u.time0 = time;
-    for (int s = 0; s < net->n_scales; ++s)
-        for (int ci = 0; ci < 6; ++ci) {
-            int W, H;
-            plane_dims(net, s, ci, W, H);
-            const int j = u.n++;
-            u.off[j] = (int64_t)(L.plane_off[6 * s + ci] / sizeof(float));
-            u.toff[j] = b.toff[6 * s + ci];
-            u.dst[j] = grads->planes[s][ci];
-            u.H[j] = H;
-            u.W[j] = W;
-            u.block0[j + 1] = u.block0[j] + (H * W + 15) / 16;
-        }
-    lsr::launch_unpack_planes(u, st);
+    unpack_planes(net, L.planes, 16, grads, u);
+    std::copy(b.toff, b.toff + u.n, u.toff);
+    lsr::launch_unpack_planes(u, 16, st);
     if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "deformation backward launch failed");
     return LSR_OK;
 }

@@ -1,6 +1,7 @@
 // deform_narrow.hip -- the deformation field at 32 plane channels per scale and a 64-wide MLP (the
 // reference's D-NeRF configs and its ModelHiddenParams defaults), language passed through.  Same
 // semantics as deform.hip (include/lsr_deform.h); its own kernels, so the 16 / 128 family is untouched.
+// What the two shapes compute the same way is shared: deform_field.h (device), deform_host.h (host).
 //
 // One block of 256 threads per 64 Gaussians, everything in fp32:
 //   features: 4 threads per Gaussian, each owning 8 of a plane's 32 channels (planes packed
@@ -13,18 +14,18 @@
 //     FMAs.  The forward reads weights transposed by lsr_deform_prepare ([in][out]); the backward's
 //     data gradients (dY W) read the torch layout [out][in], which is already [k][col] for them.
 //   backward: recompute, saved rows (features, chain activations and gradients, every head's
-//     relu(Z1) and dZ1) for the weight gradients, which are the A^T B products of deform.hip's
+//     relu(Z1) and dZ1) for the weight gradients, which are the A^T B products of deform_wgrad.hip's
 //     launch_atb (bf16 hi / lo on the matrix core, split-K over row blocks); the plane gradients are
 //     float atomics into a channel-last copy (a Gaussian's tap: 32 channels = one 128-byte line; a
 //     wave stages its 16 Gaussians in LDS so that one atomic instruction adds two whole lines),
-//     transposed and added into the torch layout by k_narrow_unpack.
+//     transposed and added into the torch layout by deform_pack.hip's k_unpack_planes<32>.
 // Every global read stays inside its tensor for S = 1..4: a tile product loads only the columns its
 // weight has (ngemm's ncol: dX = dH_0 W_0 has 32 S columns, 32 or 96 of them no multiple of the
 // 64-column tile), K runs over the weight's own rows, and row indices are clamped to P - 1.
 #include "lsr_common.h"
-#include "lsr_internal.h"
+#include "deform_field.h"
+#include "deform_host.h"
 #include "deform_narrow.h"
-#include <algorithm>
 
 namespace lsr {
 
@@ -34,7 +35,6 @@ constexpr int NW = NARROW_WIDTH;
 constexpr int NXP = NB + 4;       // LDS pitch (floats) of a transposed activation row
 constexpr int NFMAX = NC * LSR_DEFORM_MAX_SCALES;   // 128 features at most
 constexpr int NHEADS = 5;         // pos, scales, rotations, opacity, shs (no coff head: PASS only)
-constexpr int N_AABB_SLOTS = 64;  // partial rows of the box gradient, 16 floats apart
 
 struct NarrowArgs {
     int P, S, nlayers;
@@ -68,36 +68,20 @@ struct NarrowArgs {
     float* sdZ[NHEADS];               // saved [P, 64] gradient of Z1
     float* sG_rot;                    // apply_rotation: [P, 4] gradient of the rotation head's output
     float* dplanes;                   // channel-last gradient planes (offsets as planes), zeroed per call
-    float* daabb_part;                // [N_AABB_SLOTS][16], zeroed per call; null: no box gradient
+    float* daabb_part;                // [DEF_AABB_SLOTS][16], zeroed per call; null: no box gradient
 };
 
 __device__ __forceinline__ int nhead_out(int hd) { return hd < 2 ? 3 : hd == 2 ? 4 : hd == 3 ? 1 : 48; }
-__device__ constexpr int nC0(int ci) { return ci < 3 ? 0 : (ci < 5 ? 1 : 2); }
-__device__ constexpr int nC1(int ci) { return ci == 0 ? 1 : (ci == 1 || ci == 3) ? 2 : 3; }
-
-__device__ __forceinline__ void ncoords(const NarrowArgs& a, int g, float (&crd)[4]) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-        crd[c] = (a.means3D[3 * g + c] - a.aabb[c]) * (2.0f / (a.aabb[3 + c] - a.aabb[c])) - 1.0f;
-    crd[3] = a.time[g];
-}
 
 struct NTap {
     int o00, o01, o10, o11;   // float offsets of the four texels' channel 0
     float fx, fy;
 };
-// bilinear tap (grid_sample, align_corners=True, border padding)
+// the bilinear tap of deform_field.h's tap_of as offsets into a [H][W][32] plane
 __device__ __forceinline__ NTap ntap_of(const NarrowArgs& a, int pi, int ci, const float (&crd)[4]) {
-    const int W = a.pw[pi], H = a.ph[pi];
-    const float ix = fminf(fmaxf((crd[nC0(ci)] + 1.0f) * 0.5f * (float)(W - 1), 0.0f), (float)(W - 1));
-    const float iy = fminf(fmaxf((crd[nC1(ci)] + 1.0f) * 0.5f * (float)(H - 1), 0.0f), (float)(H - 1));
-    const int x0 = (int)floorf(ix), y0 = (int)floorf(iy);
-    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-    NTap t;
-    t.o00 = (y0 * W + x0) * NC; t.o01 = (y0 * W + x1) * NC;
-    t.o10 = (y1 * W + x0) * NC; t.o11 = (y1 * W + x1) * NC;
-    t.fx = ix - (float)x0; t.fy = iy - (float)y0;
-    return t;
+    const Tap t = tap_of(a, pi, ci, crd);
+    const int W = a.pw[pi];
+    return NTap{(t.y0 * W + t.x0) * NC, (t.y0 * W + t.x1) * NC, (t.y1 * W + t.x0) * NC, (t.y1 * W + t.x1) * NC, t.fx, t.fy};
 }
 struct NTexels {
     float v00[8], v01[8], v10[8], v11[8];
@@ -125,7 +109,7 @@ __device__ __forceinline__ void nfeatures(const NarrowArgs& a, int g0, float* s_
     const int tid = threadIdx.x, gl = tid >> 2, q = tid & 3;
     const int g = min(g0 + gl, a.P - 1);
     float crd[4];
-    ncoords(a, g, crd);
+    coords(a, g, crd);
     for (int s = 0; s < a.S; ++s) {
         float prod[8];
 #pragma unroll
@@ -219,11 +203,6 @@ __device__ __forceinline__ float nsmall_out(const float* ht, const float* __rest
     return s + b2[c];
 }
 
-__device__ __forceinline__ float4 nquat_mul(const float4 a, const float4 b) {
-    return make_float4(a.x * b.x - a.y * b.y - a.z * b.z - a.w * b.w, a.x * b.y + a.y * b.x + a.z * b.w - a.w * b.z,
-                       a.x * b.z - a.y * b.w + a.z * b.x + a.w * b.y, a.x * b.w + a.y * b.z - a.z * b.y + a.w * b.x);
-}
-
 __global__ void __launch_bounds__(256) k_narrow_fwd(const NarrowArgs a) {
     __shared__ __attribute__((aligned(16))) float s_x[NFMAX * NXP];
     __shared__ __attribute__((aligned(16))) float s_h[2][NW * NXP];
@@ -288,35 +267,11 @@ __global__ void __launch_bounds__(256) k_narrow_fwd(const NarrowArgs a) {
         if (quat && tid < NB && g0 + tid < a.P) {   // rotations = normalize(rotations (x) d_rot)
             const int g = g0 + tid;
             const float4 q1 = reinterpret_cast<const float4*>(a.in[2])[g];
-            const float4 p = nquat_mul(q1, make_float4(s_q[tid][0], s_q[tid][1], s_q[tid][2], s_q[tid][3]));
+            const float4 p = quat_mul(q1, make_float4(s_q[tid][0], s_q[tid][1], s_q[tid][2], s_q[tid][3]));
             const float inv = 1.0f / sqrtf(p.x * p.x + p.y * p.y + p.z * p.z + p.w * p.w);
             reinterpret_cast<float4*>(a.out[2])[g] = make_float4(p.x * inv, p.y * inv, p.z * inv, p.w * inv);
         }
     }
-}
-
-// Gradient of the rotation head's output under apply_rotation (deform.hip's quat_grad): out = p / |p|,
-// p = q1 (x) q2, q2 = the head's output; writes d_rotations and returns the head's upstream
-__device__ __forceinline__ float4 nquat_grad(const NarrowArgs& a, int g, const float* dr) {
-    const float4 q1 = reinterpret_cast<const float4*>(a.in[2])[g];
-    const float4 q2 = make_float4(dr[0], dr[1], dr[2], dr[3]);
-    const float4 p = nquat_mul(q1, q2);
-    const float inv = 1.0f / sqrtf(p.x * p.x + p.y * p.y + p.z * p.z + p.w * p.w);
-    const float4 d = reinterpret_cast<const float4*>(a.up[2])[g];
-    const float4 o = make_float4(p.x * inv, p.y * inv, p.z * inv, p.w * inv);
-    const float od = o.x * d.x + o.y * d.y + o.z * d.z + o.w * d.w;
-    const float4 dp = make_float4((d.x - o.x * od) * inv, (d.y - o.y * od) * inv, (d.z - o.z * od) * inv,
-                                  (d.w - o.w * od) * inv);
-    float d1[4], d2[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float4 ek = make_float4(k == 0, k == 1, k == 2, k == 3);
-        const float4 u = nquat_mul(ek, q2), w = nquat_mul(q1, ek);
-        d1[k] = u.x * dp.x + u.y * dp.y + u.z * dp.z + u.w * dp.w;
-        d2[k] = w.x * dp.x + w.y * dp.y + w.z * dp.z + w.w * dp.w;
-    }
-    reinterpret_cast<float4*>(a.d_rotations)[g] = make_float4(d1[0], d1[1], d1[2], d1[3]);
-    return make_float4(d2[0], d2[1], d2[2], d2[3]);
 }
 
 // Backward phase A.  LDS: the feature rows' buffer holds, in turn, the features (read by the first
@@ -375,10 +330,7 @@ __global__ void __launch_bounds__(256) k_narrow_bwd(const NarrowArgs a) {
             if (tid < NB) {
                 const int g = g0 + tid;
                 float4 G = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (g < a.P) {
-                    G = nquat_grad(a, g, s_q[tid]);
-                    reinterpret_cast<float4*>(a.sG_rot)[g] = G;
-                }
+                if (g < a.P) G = quat_grad(a, a.in[2], g, s_q[tid]);   // deform_field.h
                 s_g[0 * NXP + tid] = G.x; s_g[1 * NXP + tid] = G.y;
                 s_g[2 * NXP + tid] = G.z; s_g[3 * NXP + tid] = G.w;
             }
@@ -440,7 +392,7 @@ __global__ void __launch_bounds__(256) k_narrow_bwd(const NarrowArgs a) {
     const bool ok = g0 + gl < a.P;
     const int g = min(g0 + gl, a.P - 1);
     float crd[4];
-    ncoords(a, g, crd);
+    coords(a, g, crd);
     float dq[3] = {0.0f, 0.0f, 0.0f};
     // scatter staging, per wave, in the first hidden buffer (dead since the chain backward's last
     // barrier): the wave's 16 Gaussians' dv rows (32 channels, pitch NSP), tap offsets and weights
@@ -505,10 +457,10 @@ __global__ void __launch_bounds__(256) k_narrow_bwd(const NarrowArgs a) {
                 }
             }
             wave_lds_sync();   // staging read before the next plane rewrites it
-            const float rx = (crd[nC0(ci)] + 1.0f) * 0.5f * (float)(W - 1);
-            const float ry = (crd[nC1(ci)] + 1.0f) * 0.5f * (float)(H - 1);
-            if (nC0(ci) < 3 && rx > 0.0f && rx < (float)(W - 1)) dq[nC0(ci)] += dix * 0.5f * (float)(W - 1);
-            if (nC1(ci) < 3 && ry > 0.0f && ry < (float)(H - 1)) dq[nC1(ci)] += diy * 0.5f * (float)(H - 1);
+            const float rx = (crd[kC0(ci)] + 1.0f) * 0.5f * (float)(W - 1);
+            const float ry = (crd[kC1(ci)] + 1.0f) * 0.5f * (float)(H - 1);
+            if (kC0(ci) < 3 && rx > 0.0f && rx < (float)(W - 1)) dq[kC0(ci)] += dix * 0.5f * (float)(W - 1);
+            if (kC1(ci) < 3 && ry > 0.0f && ry < (float)(H - 1)) dq[kC1(ci)] += diy * 0.5f * (float)(H - 1);
         }
     }
 #pragma unroll
@@ -538,7 +490,7 @@ __global__ void __launch_bounds__(256) k_narrow_bwd(const NarrowArgs a) {
             for (int off = 32; off >= 1; off >>= 1) bv[k] += __shfl_xor(bv[k], off);
         }
         if ((tid & 63) == 0) {
-            float* row = a.daabb_part + (blockIdx.x % N_AABB_SLOTS) * 16;
+            float* row = a.daabb_part + (blockIdx.x % DEF_AABB_SLOTS) * 16;
 #pragma unroll
             for (int k = 0; k < 6; ++k) atomicAdd(row + k, bv[k]);
         }
@@ -561,7 +513,7 @@ __global__ void __launch_bounds__(256) k_narrow_colsum(const float* __restrict__
     if (grp == 0) atomicAdd(db + c, (s_p[0][c] + s_p[1][c]) + (s_p[2][c] + s_p[3][c]));
 }
 
-// ---- packing (lsr_deform_prepare) and the gradient planes' unpack: batched transposes ----------
+// ---- packing (lsr_deform_prepare): batched transposes ------------------------------------------
 // dst[c][r] (pitch ld, a multiple of 32) = r < rows ? src[r][c] : 0 for c < cols, r < ld: planes
 // [32][H W] -> [H W][32], Linear weights [out][in] -> [in][out pad].  A block transposes one 32 x 32
 // tile through LDS: reads run along src rows, writes along dst rows.
@@ -598,82 +550,29 @@ __global__ void __launch_bounds__(256) k_narrow_pack(const NPackBatch pb) {
     }
 }
 
-// channel-last gradient planes [H W][32] added into the torch layout [32][H W]: a block takes 8
-// texels (256 floats, read as one run), transposes them through LDS and adds 8-texel runs per
-// channel; one extra block folds the box gradient's partial rows
-struct NUnpackBatch {
-    const float* src;
-    int64_t off[24];
-    float* dst[24];
-    int hw[24];
-    int block0[25];
-    int n;
-    const float* daabb_part;
-    float* daabb;
-};
-__global__ void __launch_bounds__(256) k_narrow_unpack(const NUnpackBatch u) {
-    __shared__ float s_t[NC][9];
-    const int bid = blockIdx.x, t = threadIdx.x;
-    if (bid == u.block0[u.n]) {   // block-uniform: the box gradient (launched only with daabb set)
-        if (t < 6) {
-            float s = 0.0f;
-            for (int k = 0; k < N_AABB_SLOTS; ++k) s += u.daabb_part[k * 16 + t];
-            u.daabb[t] += s;
-        }
-        return;
-    }
-    int j = 0;
-    while (j + 1 < u.n && bid >= u.block0[j + 1]) ++j;
-    const int HW = u.hw[j], hw0 = (bid - u.block0[j]) * 8;
-    {
-        const int tx = t >> 5, ch = t & 31;
-        s_t[ch][tx] = hw0 + tx < HW ? u.src[u.off[j] + (int64_t)(hw0 + tx) * NC + ch] : 0.0f;
-    }
-    __syncthreads();
-    const int ch = t >> 3, tx = t & 7;
-    if (hw0 + tx < HW) u.dst[j][(size_t)ch * HW + hw0 + tx] += s_t[ch][tx];
-}
-
 // ==== host =========================================================================================
 namespace {
 
-constexpr int kCombos[6][2] = {{0, 1}, {0, 2}, {0, 3}, {1, 2}, {1, 3}, {2, 3}};
-constexpr int kOut[NHEADS] = {3, 3, 4, 1, 48};
-
-size_t nalign(size_t x) { return (x + 255) / 256 * 256; }
-int nl(const lsr_deform_net* n) { return std::max(n->depth, 1); }
-bool on(const lsr_deform_net* n, int hd) { return (n->heads >> hd) & 1u; }
-void pdims(const lsr_deform_net* n, int s, int ci, int& W, int& H) {
-    auto res = [&](int c) { return c < 3 ? n->res[c] * n->multires[s] : n->res[3]; };
-    W = res(kCombos[ci][0]);
-    H = res(kCombos[ci][1]);
-}
+using namespace deform_host;   // plane sizes and layout, layers, heads: shared with the 16 / 128 shape
 
 // workspace: the planes channel-last, then the transposed weights; byte offsets
 struct NLayout {
-    size_t plane[24], planes_end;
+    PlaneLayout planes;
     size_t wf_t[DEF_MAX_LAYERS], w1_t[NHEADS], w2_t[NHEADS];
     size_t total;
 };
 NLayout nlayout(const lsr_deform_net* n) {
     NLayout L{};
-    size_t o = 0;
-    for (int s = 0; s < n->n_scales; ++s)
-        for (int ci = 0; ci < 6; ++ci) {
-            int W, H;
-            pdims(n, s, ci, W, H);
-            L.plane[6 * s + ci] = o;
-            o += nalign((size_t)W * H * NC * sizeof(float));
-        }
-    L.planes_end = o;
+    L.planes = plane_layout(n, NC);
+    size_t o = L.planes.end;
     auto take = [&](size_t floats) {
         const size_t at = o;
-        o += nalign(floats * sizeof(float));
+        o += align256(floats * sizeof(float));
         return at;
     };
-    for (int k = 0; k < nl(n); ++k) L.wf_t[k] = take((size_t)(k == 0 ? NC * n->n_scales : NW) * NW);
+    for (int k = 0; k < nlayers(n); ++k) L.wf_t[k] = take((size_t)(k == 0 ? NC * n->n_scales : NW) * NW);
     for (int hd = 0; hd < NHEADS; ++hd) {
-        if (!on(n, hd)) continue;
+        if (!head_on(n, hd)) continue;
         L.w1_t[hd] = take((size_t)NW * NW);
         L.w2_t[hd] = take((size_t)NW * NW);
     }
@@ -689,23 +588,23 @@ NScratch nscratch(const lsr_deform_net* n, size_t P) {
     size_t o = 0;
     auto take = [&](size_t floats) {
         const size_t at = o;
-        o += nalign(floats * sizeof(float));
+        o += align256(floats * sizeof(float));
         return at;
     };
     s.X = take(P * NC * n->n_scales);
-    for (int k = 0; k < nl(n); ++k) {
+    for (int k = 0; k < nlayers(n); ++k) {
         s.A[k] = take(P * NW);
         s.dH[k] = take(P * NW);
     }
     for (int hd = 0; hd < NHEADS; ++hd) {
-        if (!on(n, hd)) continue;
+        if (!head_on(n, hd)) continue;
         s.R[hd] = take(P * NW);
         s.dZ[hd] = take(P * NW);
     }
     s.Grot = take(n->apply_rotation ? P * 4 : 1);
-    s.daabb = take(N_AABB_SLOTS * 16);   // zeroed with the gradient planes (contiguous)
+    s.daabb = take(DEF_AABB_SLOTS * 16);   // zeroed with the gradient planes (contiguous)
     s.dplanes = o;
-    o += nlayout(n).planes_end;
+    o += nlayout(n).planes.end;
     s.total = o;
     return s;
 }
@@ -717,26 +616,19 @@ NarrowArgs nargs(const lsr_deform_net* net, const void* workspace, int32_t P) {
     NarrowArgs a{};
     a.P = P;
     a.S = net->n_scales;
-    a.nlayers = nl(net);
+    a.nlayers = nlayers(net);
     a.heads = net->heads;
     a.apply_rotation = net->apply_rotation;
     a.aabb = net->aabb;
     a.planes = fp(0);
-    for (int s = 0; s < net->n_scales; ++s)
-        for (int ci = 0; ci < 6; ++ci) {
-            int W, H;
-            pdims(net, s, ci, W, H);
-            a.poff[6 * s + ci] = (int64_t)(L.plane[6 * s + ci] / sizeof(float));
-            a.pw[6 * s + ci] = W;
-            a.ph[6 * s + ci] = H;
-        }
+    plane_args(net, L.planes, a.poff, a.pw, a.ph);
     for (int k = 0; k < a.nlayers; ++k) {
         a.wf_t[k] = fp(L.wf_t[k]);
         a.wf[k] = net->w_feat[k];
         a.b_feat[k] = net->b_feat[k];
     }
     for (int hd = 0; hd < NHEADS; ++hd) {
-        if (!on(net, hd)) continue;
+        if (!head_on(net, hd)) continue;
         a.w1_t[hd] = fp(L.w1_t[hd]);
         a.w2_t[hd] = fp(L.w2_t[hd]);
         a.w1[hd] = net->w1[hd];
@@ -767,14 +659,14 @@ void narrow_prepare(const lsr_deform_net* net, void* workspace, hipStream_t st) 
     for (int s = 0; s < net->n_scales; ++s)
         for (int ci = 0; ci < 6; ++ci) {
             int W, H;
-            pdims(net, s, ci, W, H);
-            job(net->planes[s][ci], L.plane[6 * s + ci], NC, W * H, NC);
+            plane_dims(net, s, ci, W, H);
+            job(net->planes[s][ci], L.planes.off[6 * s + ci], NC, W * H, NC);
         }
-    for (int k = 0; k < nl(net); ++k) job(net->w_feat[k], L.wf_t[k], NW, k == 0 ? NC * net->n_scales : NW, NW);
+    for (int k = 0; k < nlayers(net); ++k) job(net->w_feat[k], L.wf_t[k], NW, k == 0 ? NC * net->n_scales : NW, NW);
     for (int hd = 0; hd < NHEADS; ++hd) {
-        if (!on(net, hd)) continue;
+        if (!head_on(net, hd)) continue;
         job(net->w1[hd], L.w1_t[hd], NW, NW, NW);
-        job(net->w2[hd], L.w2_t[hd], kOut[hd], NW, NW);
+        job(net->w2[hd], L.w2_t[hd], kHeadOut[hd], NW, NW);
     }
     hipLaunchKernelGGL(k_narrow_pack, dim3(blocks), dim3(256), 0, st, pb);
 }
@@ -815,7 +707,7 @@ hipError_t narrow_backward(const lsr_deform_net* net, const void* workspace, int
         a.sdH[k] = fp(S.dH[k]);
     }
     for (int hd = 0; hd < NHEADS; ++hd) {
-        if (!on(net, hd)) continue;
+        if (!head_on(net, hd)) continue;
         a.sR[hd] = fp(S.R[hd]);
         a.sdZ[hd] = fp(S.dZ[hd]);
     }
@@ -826,7 +718,7 @@ hipError_t narrow_backward(const lsr_deform_net* net, const void* workspace, int
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_narrow_bwd, dim3((P + NB - 1) / NB), dim3(256), 0, st, a);
 
-    // weight gradients: A^T B products of the saved rows, split-K over row blocks (deform.hip's k_atb)
+    // weight gradients: A^T B products of the saved rows, split-K over row blocks (deform_wgrad.hip's k_atb)
     AtbArgs g{};
     g.P = P;
     const int64_t per = ((int64_t)P + 1023) / 1024;
@@ -840,29 +732,21 @@ hipError_t narrow_backward(const lsr_deform_net* net, const void* workspace, int
         hipLaunchKernelGGL(k_narrow_colsum, dim3((P + NCOLSUM_ROWS - 1) / NCOLSUM_ROWS), dim3(256), 0, st, a.sdH[0], P,
                            grads->b_feat[0]);
     for (int hd = 0; hd < NHEADS; ++hd) {
-        if (!on(net, hd)) continue;
+        if (!head_on(net, hd)) continue;
         const float* G = (hd == 2 && net->apply_rotation) ? a.sG_rot : up[hd];
         g.job[nj++] = AtbJob{a.sdZ[hd], a.sA[a.nlayers - 1], grads->w1[hd], grads->b1[hd], NW, NW};
-        g.job[nj++] = AtbJob{G, a.sR[hd], grads->w2[hd], grads->b2[hd], kOut[hd], NW};
+        g.job[nj++] = AtbJob{G, a.sR[hd], grads->w2[hd], grads->b2[hd], kHeadOut[hd], NW};
     }
     static_assert(DEF_MAX_LAYERS + 2 * NHEADS <= LSR_ATB_MAX_JOBS, "one launch holds every job");
     launch_atb(g, nj, st);
 
-    NUnpackBatch u{};
+    UnpackBatch u{};   // one copy of the gradient planes, no time rows
     u.src = a.dplanes;
+    u.replicas = 1;
     u.daabb_part = a.daabb_part;
     u.daabb = grads->aabb;
-    for (int s = 0; s < net->n_scales; ++s)
-        for (int ci = 0; ci < 6; ++ci) {
-            int W, H;
-            pdims(net, s, ci, W, H);
-            const int j = u.n++;
-            u.off[j] = (int64_t)(L.plane[6 * s + ci] / sizeof(float));
-            u.dst[j] = grads->planes[s][ci];
-            u.hw[j] = H * W;
-            u.block0[j + 1] = u.block0[j] + (H * W + 7) / 8;
-        }
-    hipLaunchKernelGGL(k_narrow_unpack, dim3(u.block0[u.n] + (grads->aabb ? 1 : 0)), dim3(256), 0, st, u);
+    unpack_planes(net, L.planes, NC, grads, u);
+    launch_unpack_planes(u, NC, st);
     return hipSuccess;
 }
 

@@ -1,5 +1,5 @@
 """The hand-over into the discrete language stage: the status centres of every Gaussian, on the MI355X
-(csrc/deform.hip k_centers_from_field, csrc/centers.hip; C-ABI include/lsr_centers.h).
+(csrc/deform_lang.hip k_centers_from_field, csrc/centers.hip; C-ABI include/lsr_centers.h).
 
 Replaces GaussianModel.generate_multi_feature_centers (scene/gaussian_model.py:804-845) and the
 discrete branch of training_setup (:226-231):

@@ -72,6 +72,21 @@ def test_changed_metadata_is_a_diff(tmp_path):
     assert "DIFF  k_tILb1EE" in out and "group_segment_fixed_size: 1024 -> 2048" in out
 
 
+def test_a_side_may_be_several_listings(tmp_path):
+    """k_a and k_b, one listing per kernel on either side, joined with `+`: both are found with their
+    own metadata, and a change in the second listing is still a DIFF."""
+    for name, text in (("old_a.s", dict(OLD, name="k_a")), ("old_b.s", dict(OLD, name="k_b", idx=4, lds=512)),
+                       ("a.s", dict(OLD, name="k_a", idx=0))):
+        (tmp_path / name).write_text(ASM.format(**text))
+    for lds, want in ((512, 0), (256, 1)):
+        (tmp_path / "b.s").write_text(ASM.format(**dict(OLD, name="k_b", idx=0, lds=lds)))
+        r = subprocess.run([sys.executable, TOOL, f"{tmp_path / 'old_a.s'}+{tmp_path / 'old_b.s'}",
+                            f"{tmp_path / 'a.s'}+{tmp_path / 'b.s'}"], capture_output=True, text=True)
+        assert r.returncode == want, r.stdout
+        assert "same  k_a" in r.stdout and ("same  k_b" if want == 0 else "DIFF  k_b") in r.stdout
+        assert "2 -> 2 kernels" in r.stdout
+
+
 def test_unmapped_kernel_is_gone_and_new(tmp_path):
     code, out = _run(tmp_path, OLD, dict(OLD, name="k_t"))
     assert code != 0

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Are the kernels of two device assembly files (hipcc ... --cuda-device-only -S) the same code?
     python tools/asm_same.py old.s new.s [old_symbol=new_symbol ...]
+Either side may be several listings joined with `+` (old.s new_a.s+new_b.s: a unit that was split).
 Per kernel: same / DIFF (first differing lines) / gone / new, over the function's text from `name:`
 to .Lfunc_end (without comments, blank lines, section / symbol directives, the function's index in
 .LBB labels and its own name) and its amdhsa.kernels metadata.  Text only: no instruction is looked
@@ -37,10 +38,19 @@ def metadata(text):
     return out
 
 
+def side(paths):
+    """functions and metadata of the listings `a.s+b.s+...` (a unit split into several, or joined)"""
+    fns, meta = {}, {}
+    for p in paths.split("+"):
+        text = open(p).read()
+        fns.update(functions(text))
+        meta.update(metadata(text))
+    return fns, meta
+
+
 def main():
-    old, new = open(sys.argv[1]).read(), open(sys.argv[2]).read()
     rename = dict(a.split("=", 1) for a in sys.argv[3:])
-    fo, fn, mo, mn = functions(old), functions(new), metadata(old), metadata(new)
+    (fo, mo), (fn, mn) = side(sys.argv[1]), side(sys.argv[2])
     bad, seen = 0, set()
     for name, lo in fo.items():
         to = rename.get(name, name)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The status centres at the headline size (csrc/deform.hip k_centers_from_field): P = 2M Gaussians,
+"""The status centres at the headline size (csrc/deform_lang.hip k_centers_from_field): P = 2M Gaussians,
 S = 100 sample times, K = 3 centres, lang_dim D = 3 and D = 6, a RESIDUAL field.
 
 Both sides are timed on the same card in one process, ROUNDS rounds after a warm-up, alternating, with
