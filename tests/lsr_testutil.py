@@ -242,6 +242,56 @@ def grad_check(native, ref, abs_terms=None):
     return bad, stats
 
 
+DEFORM_COEF = 1e-4
+
+
+def deform_check(native, ref, A, coef=DEFORM_COEF):
+    """Per-element check of the deformation field's outputs (as offsets) or gradients against the
+    oracle; native, ref and A are dicts name -> array (entries of `native` that are None are skipped),
+    ref from DeformOracle(coords="float32") and A its term scales (abs_terms=True).  Per element
+        |native - ref| <= 1e-4 |ref| + coef A
+    and exactly 0 where A = 0 (nothing flows into the element: a plane cell no Gaussian touches, a
+    coordinate behind a border mask); a non-finite value fails.
+
+    coef.  DEFORM_COEF = 1e-4 is grad_check's coefficient, the project's figure for sums of bf16
+    hi / lo products (measured at 2.6e-5 A on the compositors).  It stands on a CPU judgement, not on
+    the kernels' error: the oracle's products="bf16x3" emulation (every Linear product, forward and
+    backward, as hi hi + hi lo + lo hi of bf16 halves accumulated in float32 -- it overstates the
+    kernels, whose small heads form G W2 in fp32) against the float64 oracle on the same float32
+    coordinates stays under half of it on every case of tests/deform_cases.py with P <= 12,300:
+    largest err / A 2.3e-5 (tests/test_deform_check.py asserts the half and prints the figures).  One
+    product of hi / lo halves is off by at most ~2^-16 of its magnitude and a chain of up to nine
+    layers (forward and back) adds the layers' shares, all relative to A because A is carried through
+    the chain; errors of the 16..128 products of an element do not line up, hence the distance to
+    the worst case.  The 32 / 64 shape runs its MLP in fp32 and takes the same coefficient.  grid.aabb
+    has a term scale of its own (DeformOracle's docstring), of which the emulation reaches 8.9e-6.
+
+    Returns (bad, stats): bad[name] = dict(elements, first=[(index, native, ref, A, err / A)...]);
+    stats[name] = dict(max_err_over_A, rel) with rel the tensor-wide max |err| / max |ref|."""
+    bad, stats = {}, {}
+    for key, n in native.items():
+        if n is None:
+            continue
+        r = np.asarray(ref[key], np.float64)
+        a = np.asarray(A[key], np.float64).reshape(r.shape)
+        n = np.asarray(_np(n), np.float64).reshape(r.shape)
+        if r.size == 0:
+            continue
+        assert (a >= np.abs(r) * (1 - 1e-9) - 1e-300).all(), key           # |sum| <= sum |term|
+        finite = np.isfinite(n)
+        err = np.where(finite, np.abs(np.where(finite, n, 0.0) - r), np.inf)
+        pos = a > 0
+        ratio = np.where(pos, err / np.where(pos, a, 1.0), 0.0)
+        stats[key] = dict(max_err_over_A=float(ratio.max()), rel=float(err.max() / max(np.abs(r).max(), 1e-30)))
+        over = ~(err <= 1e-4 * np.abs(r) + coef * a) | (~pos & (n != 0))
+        if over.any():
+            idx = np.argwhere(over)
+            bad[key] = dict(elements=int(over.sum()),
+                            first=[(tuple(int(i) for i in ix), float(n[tuple(ix)]), float(r[tuple(ix)]),
+                                    float(a[tuple(ix)]), float(ratio[tuple(ix)])) for ix in idx[:6]])
+    return bad, stats
+
+
 U24 = 2.0 ** -24          # fp32 unit roundoff
 IMAGE_COEF_MAX = 1e-4     # the cap of the derived coefficient; the matrix-core language coefficient
 IMAGE_COEF_C = 8          # the constant c of image_coef

@@ -11,6 +11,7 @@ import torch
 
 from deform_oracle import DeformConfig, DeformOracle
 from deformation import HEADS, HEAD_OUT, LANG_PASS, LANG_RESIDUAL, DeformationField
+from lsr_testutil import DEFORM_COEF, U24, deform_check
 from test_deform_gpu import _morton
 from test_deform_narrow import VARIANTS, load_variant
 
@@ -230,6 +231,27 @@ def _check_against_oracle(multires, P, morton=False, **kw):
     n = (inp["means3D"] - aabb[0]) * (2.0 / (aabb[1] - aabb[0])) - 1.0
     want = np.stack([(0.5 * gq * (n - 1.0)).sum(0), (-0.5 * gq * (n + 1.0)).sum(0)])
     assert _rel(grads["grid.aabb"], want) < 1e-4
+    # per element as well (lsr_testutil.deform_check, as tests/test_deform_branches_gpu.py): against the oracle
+    # on the kernels' float32 cells, with its term scales, the same masked upstream, and its box gradient
+    o32 = DeformOracle(params, aabb, cfg=cfg, coords="float32", train_aabb=True)
+    r32, A_out = o32.forward(*[inp[k] for k in KEYS], None, times, abs_terms=True)
+    g_in32, g_p32, A_in, A_p = o32.backward(*[ups[k] for k in KEYS], abs_terms=True)
+    plain = [k for k in KEYS if not (k == "rotations" and cfg.apply_rotation)]
+    nat = {k: g.cpu().numpy().astype(np.float64).reshape(inp[k].shape) for k, g in zip(KEYS, out)}
+    for k in KEYS:   # a stored residual output fl(input + offset) carries that one rounding beside coef A
+        A_out[k] = A_out[k] + (A_out[k] > 0) * (U24 / DEFORM_COEF) * np.abs(r32[k])
+    bad, _ = deform_check({k: nat[k] - inp[k] if k in plain else nat[k] for k in KEYS},
+                          {k: r32[k] - inp[k] if k in plain else r32[k] for k in KEYS}, A_out)
+    assert not bad, bad
+    nat_in = {"means3D": got[0].cpu().numpy()}
+    if cfg.apply_rotation:
+        nat_in["rotations"] = got[2].cpu().numpy()
+    bad, _ = deform_check(nat_in, g_in32, A_in)
+    assert not bad, bad
+    assert set(grads) == set(g_p32)
+    bad, _ = deform_check(grads, g_p32, A_p)
+    assert not bad, bad
+    assert _rel(grads["grid.aabb"], g_p32["grid.aabb"]) < 1e-4
     return f
 
 
