@@ -10,12 +10,12 @@
 #include "../../include/lsr_centers.h"
 #include "centers_kmeans.h"
 #include "deform_internal.h"
+#include "lsr_host.h"
 
 static_assert(lsr::CK_MAX_K == LSR_CENTERS_MAX_K && lsr::CK_MAX_S == LSR_CENTERS_MAX_SAMPLES &&
                   lsr::CK_MAX_D == LSR_CENTERS_MAX_DIM, "the kernel's limits are the header's");
 
 namespace lsr {
-int fail(int code, const std::string& msg);   // lsr_api.hip (thread-local lsr_last_error)
 int deform_lang_args(const lsr_deform_net* net, const void* workspace, int32_t P, LangDeformArgs* out);   // deform_api.hip
 
 namespace {
@@ -66,8 +66,7 @@ extern "C" int lsr_centers_kmeans(const float* x, int32_t P, int32_t S, int32_t 
     const int rpb = std::max(1, std::min(lsr::KM_WAVES, lsr::CK_XFLOATS / (S * lsr::ck_pitch(D))));
     hipLaunchKernelGGL(lsr::k_centers_kmeans, dim3((P + rpb - 1) / rpb), dim3(64 * lsr::KM_WAVES), 0,
                        reinterpret_cast<hipStream_t>(stream), x, P, S, D, K, max_iter, rpb, centers, counts, inertia, iters);
-    if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "centres: k-means launch failed");
-    return LSR_OK;
+    return lsr::launched("centres: k-means launch failed");
 }
 
 extern "C" int lsr_centers_from_field(const lsr_deform_net* net, const void* workspace, int32_t P, const float* lang,
@@ -98,6 +97,5 @@ extern "C" int lsr_centers_from_field(const lsr_deform_net* net, const void* wor
     a.samples_out = samples_out;
     a.times_out = times_out;
     lsr::launch_centers_from_field(a, reinterpret_cast<hipStream_t>(stream));
-    if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "centres: fused launch failed");
-    return LSR_OK;
+    return lsr::launched("centres: fused launch failed");
 }

@@ -1,5 +1,4 @@
 // deform_api.hip -- C ABI of the deformation field (include/lsr_deform.h).
-#include <atomic>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,13 +12,11 @@
 
 static_assert(lsr::DEF_UNPACK_MAX == 6 * LSR_DEFORM_MAX_SCALES, "one unpack slot per plane");
 
-namespace lsr {
-int fail(int code, const std::string& msg);   // lsr_api.hip (thread-local lsr_last_error)
-}
-
 namespace {
 
 using namespace lsr::deform_host;   // plane sizes and layout, layers, heads: shared with the 32 / 64 shape
+using lsr::Carver;
+using lsr::launched;
 
 constexpr int kW = 128;   // MLP width
 
@@ -34,9 +31,9 @@ int lang_in(const lsr_deform_net* n) {
     return n->lang_mode == LSR_DEFORM_LANG_DISCRETE ? n->lang_dim * n->centers : n->lang_dim;
 }
 
-// one packed bf16 hi / lo pair of `count` elements
+// one packed bf16 hi / lo pair: the byte offsets of its halves
 struct Pack {
-    size_t off = 0, count = 0;
+    size_t hi = 0, lo = 0;
 };
 struct Layout {
     PlaneLayout planes;     // channel-last [H][W][16]
@@ -49,11 +46,11 @@ struct Layout {
 Layout layout(const lsr_deform_net* n) {
     Layout L{};
     L.planes = plane_layout(n, 16);
-    size_t o = L.planes.end;
+    Carver c;
+    c.skip(L.planes.end);
     auto take = [&](Pack& p, size_t count) {
-        p.off = o;
-        p.count = count;
-        o += align256(count * sizeof(__bf16)) * 2;
+        p.hi = c.skip(count * sizeof(__bf16));
+        p.lo = c.skip(count * sizeof(__bf16));
     };
     const int F = feat_dim(n), Fpad = (F + 31) / 32 * 32;
     for (int k = 0; k < nlayers(n); ++k) {
@@ -76,17 +73,16 @@ Layout layout(const lsr_deform_net* n) {
         take(L.wlt[1], (size_t)kW * kW);
         take(L.wlt[2], (size_t)kW * 32);
     }
-    L.total = o;
+    L.total = c.total();
     return L;
 }
 
-// the lsr_deform.h version the caller declared (lsr_deform_require_api); 0 = none yet
-std::atomic<int> g_deform_caller_api{0};
+// the lsr_deform.h version the caller declared (lsr_deform_require_api)
+lsr::ApiGate g_deform_api{"lsr_deform", "LSR_DEFORM_API_VERSION", LSR_DEFORM_API_VERSION,
+                          "lsr_deform.h version " + std::to_string(LSR_DEFORM_API_VERSION)};
 
 int check(const lsr_deform_net* n) {
-    if (g_deform_caller_api.load() != LSR_DEFORM_API_VERSION)   // the structs' layout is this header's only
-        return lsr::fail(LSR_EINVAL, "call lsr_deform_require_api(LSR_DEFORM_API_VERSION) first: the caller must be "
-                                     "built against lsr_deform.h version " + std::to_string(LSR_DEFORM_API_VERSION));
+    if (int rc = g_deform_api.check()) return rc;   // the structs' layout is this header's only
     if (!n) return lsr::fail(LSR_EINVAL, "null deformation net");
     const bool narrow = lsr::deform_is_narrow(n);
     if (n->n_scales < 1 || n->n_scales > LSR_DEFORM_MAX_SCALES || ((n->channels != 16 || n->width != kW) && !narrow))
@@ -144,8 +140,7 @@ extern "C" int lsr_deform_prepare(const lsr_deform_net* net, void* workspace, vo
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (lsr::deform_is_narrow(net)) {
         lsr::narrow_prepare(net, workspace, st);
-        if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "deformation packing launch failed");
-        return LSR_OK;
+        return launched("deformation packing launch failed");
     }
     const Layout L = layout(net);
     char* ws = reinterpret_cast<char*>(workspace);
@@ -166,8 +161,8 @@ extern "C" int lsr_deform_prepare(const lsr_deform_net* net, void* workspace, vo
             plane_dims(net, s, ci, W, H);
             plane(net->planes[s][ci], reinterpret_cast<float*>(ws + L.planes.off[6 * s + ci]), H, W);
         }
-    auto hi = [&](const Pack& p) { return reinterpret_cast<__bf16*>(ws + p.off); };
-    auto lo = [&](const Pack& p) { return reinterpret_cast<__bf16*>(ws + p.off + align256(p.count * sizeof(__bf16))); };
+    auto hi = [&](const Pack& p) { return reinterpret_cast<__bf16*>(ws + p.hi); };
+    auto lo = [&](const Pack& p) { return reinterpret_cast<__bf16*>(ws + p.lo); };
     const int F = feat_dim(net), Fpad = (F + 31) / 32 * 32;
     constexpr int PW = lsr::PACK_WEIGHT, PT = lsr::PACK_WEIGHT_T;
     for (int k = 0; k < nlayers(net); ++k) {
@@ -193,18 +188,15 @@ extern "C" int lsr_deform_prepare(const lsr_deform_net* net, void* workspace, vo
         wt(PT, net->w_lang[2], hi(L.wlt[2]), lo(L.wlt[2]), C, kW, 32, kW);
     }
     lsr::launch_pack_batch(jobs.data(), (int)jobs.size(), st);
-    if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "deformation packing launch failed");
-    return LSR_OK;
+    return launched("deformation packing launch failed");
 }
 
 namespace {
 
 template <typename T>
-const T* chi(const char* ws, const Pack& p) { return reinterpret_cast<const T*>(ws + p.off); }
+const T* chi(const char* ws, const Pack& p) { return reinterpret_cast<const T*>(ws + p.hi); }
 template <typename T>
-const T* clo(const char* ws, const Pack& p) {
-    return reinterpret_cast<const T*>(ws + p.off + align256(p.count * sizeof(__bf16)));
-}
+const T* clo(const char* ws, const Pack& p) { return reinterpret_cast<const T*>(ws + p.lo); }
 
 // forward kernel arguments common to the forward and the backward (planes, packed weights, biases)
 lsr::DeformArgs forward_args(const lsr_deform_net* net, const void* workspace, int32_t P) {
@@ -283,13 +275,8 @@ size_t time_row_floats(const lsr_deform_net* net, int64_t* toff) {
 }
 BwdScratch bwd_scratch(const lsr_deform_net* net, size_t P) {
     BwdScratch s{};
-    size_t o = 0;
-    const size_t f = sizeof(float);
-    auto take = [&](size_t floats) {
-        const size_t at = o;
-        o += align256(floats * f);
-        return at;
-    };
+    Carver c;
+    auto take = [&](size_t floats) { return c.skip(floats * sizeof(float)); };
     s.X = take(P * feat_dim(net));
     for (int k = 0; k < nlayers(net); ++k) {
         s.A[k] = take(P * kW);
@@ -306,11 +293,9 @@ BwdScratch bwd_scratch(const lsr_deform_net* net, size_t P) {
         s.dZ1l = take(P * kW);
     }
     s.daabb = take(lsr::DEF_AABB_SLOTS * 16);   // zeroed with the gradient planes (contiguous)
-    s.dplanes = o;
-    o += (size_t)kGradReplicas * layout(net).planes.end;
-    s.trow = o;                                                  // zeroed with the planes (contiguous)
-    o += align256((size_t)kTimeRowReps * time_row_floats(net, nullptr) * f);
-    s.total = o;
+    s.dplanes = c.skip((size_t)kGradReplicas * plane_layout(net, 16).end);
+    s.trow = take((size_t)kTimeRowReps * time_row_floats(net, nullptr));   // zeroed with the planes (contiguous)
+    s.total = c.total();
     return s;
 }
 
@@ -332,13 +317,7 @@ int deform_lang_args(const lsr_deform_net* net, const void* workspace, int32_t P
 }
 }  // namespace lsr
 
-extern "C" int lsr_deform_require_api(int32_t caller_version) {
-    if (caller_version != LSR_DEFORM_API_VERSION)
-        return lsr::fail(LSR_EINVAL, "lsr_deform.h version mismatch: caller " + std::to_string(caller_version) +
-                                         ", library " + std::to_string(LSR_DEFORM_API_VERSION));
-    g_deform_caller_api.store(caller_version);
-    return LSR_OK;
-}
+extern "C" int lsr_deform_require_api(int32_t caller_version) { return g_deform_api.require(caller_version); }
 
 extern "C" int lsr_deform_forward(const lsr_deform_net* net, const void* workspace, int32_t P, const float* means3D,
                                   const float* scales, const float* rotations, const float* opacity,
@@ -360,8 +339,7 @@ extern "C" int lsr_deform_forward(const lsr_deform_net* net, const void* workspa
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (lsr::deform_is_narrow(net)) {
         lsr::narrow_forward(net, workspace, P, means3D, time, ins, outs, st);
-        if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "deformation forward launch failed");
-        return LSR_OK;
+        return launched("deformation forward launch failed");
     }
     lsr::DeformArgs a = forward_args(net, workspace, P);
     a.means3D = means3D;
@@ -381,8 +359,7 @@ extern "C" int lsr_deform_forward(const lsr_deform_net* net, const void* workspa
         la.out_lang = out_lang;
         lsr::launch_lang_deform_fwd(la, st);
     }
-    if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "deformation forward launch failed");
-    return LSR_OK;
+    return launched("deformation forward launch failed");
 }
 
 extern "C" int64_t lsr_deform_backward_scratch_bytes(const lsr_deform_net* net, int32_t P) {
@@ -427,8 +404,7 @@ extern "C" int lsr_deform_backward(const lsr_deform_net* net, const void* worksp
         if (lsr::narrow_backward(net, workspace, P, means3D, rotations, time, ups, d_means3D, d_rotations, grads, scratch,
                                  st) != hipSuccess)
             return lsr::fail(LSR_EHIP, "memset");
-        if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "deformation backward launch failed");
-        return LSR_OK;
+        return launched("deformation backward launch failed");
     }
     const Layout L = layout(net);
     const BwdScratch S = bwd_scratch(net, (size_t)P);
@@ -527,6 +503,5 @@ extern "C" int lsr_deform_backward(const lsr_deform_net* net, const void* worksp
     unpack_planes(net, L.planes, 16, grads, u);
     std::copy(b.toff, b.toff + u.n, u.toff);
     lsr::launch_unpack_planes(u, 16, st);
-    if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "deformation backward launch failed");
-    return LSR_OK;
+    return launched("deformation backward launch failed");
 }

@@ -6,6 +6,7 @@
 
 #include "../../include/lsr_deform.h"
 #include "deform_internal.h"
+#include "lsr_host.h"
 
 namespace lsr {
 namespace deform_host {
@@ -13,7 +14,6 @@ namespace deform_host {
 constexpr int kCombos[6][2] = {{0, 1}, {0, 2}, {0, 3}, {1, 2}, {1, 3}, {2, 3}};   // xy, xz, xt, yz, yt, zt
 constexpr int kHeadOut[5] = {3, 3, 4, 1, 48};   // pos, scales, rotations, opacity, shs
 
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 inline int nlayers(const lsr_deform_net* n) { return std::max(n->depth, 1); }
 inline bool head_on(const lsr_deform_net* n, int hd) { return (n->heads >> hd) & 1u; }
 
@@ -30,13 +30,14 @@ struct PlaneLayout {
 };
 inline PlaneLayout plane_layout(const lsr_deform_net* n, int channels) {
     PlaneLayout L{};
+    Carver c;
     for (int s = 0; s < n->n_scales; ++s)
         for (int ci = 0; ci < 6; ++ci) {
             int W, H;
             plane_dims(n, s, ci, W, H);
-            L.off[6 * s + ci] = L.end;
-            L.end += align256((size_t)W * H * channels * sizeof(float));
+            L.off[6 * s + ci] = c.skip((size_t)W * H * channels * sizeof(float));
         }
+    L.end = c.total();
     return L;
 }
 // the kernels' view of them: float offsets, widths and heights

@@ -564,19 +564,16 @@ struct NLayout {
 NLayout nlayout(const lsr_deform_net* n) {
     NLayout L{};
     L.planes = plane_layout(n, NC);
-    size_t o = L.planes.end;
-    auto take = [&](size_t floats) {
-        const size_t at = o;
-        o += align256(floats * sizeof(float));
-        return at;
-    };
-    for (int k = 0; k < nlayers(n); ++k) L.wf_t[k] = take((size_t)(k == 0 ? NC * n->n_scales : NW) * NW);
+    Carver c;
+    c.skip(L.planes.end);
+    auto floats = [&](size_t count) { return c.skip(count * sizeof(float)); };
+    for (int k = 0; k < nlayers(n); ++k) L.wf_t[k] = floats((size_t)(k == 0 ? NC * n->n_scales : NW) * NW);
     for (int hd = 0; hd < NHEADS; ++hd) {
         if (!head_on(n, hd)) continue;
-        L.w1_t[hd] = take((size_t)NW * NW);
-        L.w2_t[hd] = take((size_t)NW * NW);
+        L.w1_t[hd] = floats((size_t)NW * NW);
+        L.w2_t[hd] = floats((size_t)NW * NW);
     }
-    L.total = o;
+    L.total = c.total();
     return L;
 }
 
@@ -585,27 +582,22 @@ struct NScratch {
 };
 NScratch nscratch(const lsr_deform_net* n, size_t P) {
     NScratch s{};
-    size_t o = 0;
-    auto take = [&](size_t floats) {
-        const size_t at = o;
-        o += align256(floats * sizeof(float));
-        return at;
-    };
-    s.X = take(P * NC * n->n_scales);
+    Carver c;
+    auto floats = [&](size_t count) { return c.skip(count * sizeof(float)); };
+    s.X = floats(P * NC * n->n_scales);
     for (int k = 0; k < nlayers(n); ++k) {
-        s.A[k] = take(P * NW);
-        s.dH[k] = take(P * NW);
+        s.A[k] = floats(P * NW);
+        s.dH[k] = floats(P * NW);
     }
     for (int hd = 0; hd < NHEADS; ++hd) {
         if (!head_on(n, hd)) continue;
-        s.R[hd] = take(P * NW);
-        s.dZ[hd] = take(P * NW);
+        s.R[hd] = floats(P * NW);
+        s.dZ[hd] = floats(P * NW);
     }
-    s.Grot = take(n->apply_rotation ? P * 4 : 1);
-    s.daabb = take(DEF_AABB_SLOTS * 16);   // zeroed with the gradient planes (contiguous)
-    s.dplanes = o;
-    o += nlayout(n).planes.end;
-    s.total = o;
+    s.Grot = floats(n->apply_rotation ? P * 4 : 1);
+    s.daabb = floats(DEF_AABB_SLOTS * 16);   // zeroed with the gradient planes (contiguous)
+    s.dplanes = c.skip(plane_layout(n, NC).end);
+    s.total = c.total();
     return s;
 }
 

@@ -22,12 +22,13 @@
 
 #include "../../include/lsr.h"
 #include "../../include/lsr_train.h"
-
-namespace lsr {
-int fail(int code, const std::string& msg);   // lsr_api.hip (thread-local lsr_last_error)
-}
+#include "lsr_host.h"
+#include "lsr_wave.h"
 
 namespace {
+
+using lsr::launched;
+using lsr::wave_sum;
 
 constexpr int IL_MAX_VIEWS = 8, IL_THREADS = 256, IL_WAVES = IL_THREADS / 64;
 constexpr int IL_R = 5, IL_TAPS = 2 * IL_R + 1;            // the 11-tap window
@@ -62,14 +63,6 @@ struct ImageLossArgs {
     const float* d_l1;
     const float* d_ssim;
 };
-
-size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // Stage the 26 x 74 halo tile of `src` (an [H, W] plane) whose interior starts at (h0, w0); zeros outside.
 // Every lane's loads (8 of them) are issued before the first LDS store, so that they are in flight together.
@@ -283,20 +276,13 @@ __global__ void __launch_bounds__(IL_THREADS) k_image_loss_bwd(ImageLossArgs a) 
     }
 }
 
-struct ImageLossWs {
-    double* partial;
-    float* maps;
-    size_t bytes;
-};
-ImageLossWs carve(void* base, int64_t V, int64_t C, int64_t H, int64_t W) {
-    char* b = static_cast<char*>(base);
+// the workspace carved into a's block sums and maps; returns its bytes
+size_t carve(ImageLossArgs& a, void* base, int64_t V, int64_t C, int64_t H, int64_t W) {
     const int64_t tiles = ((W + IL_TW - 1) / IL_TW) * ((H + IL_TH - 1) / IL_TH);
-    const size_t part = al256((size_t)(V * C * tiles) * 3 * sizeof(double));
-    ImageLossWs w{};
-    w.partial = reinterpret_cast<double*>(b);
-    w.maps = reinterpret_cast<float*>(b ? b + part : nullptr);
-    w.bytes = part + al256((size_t)(V * C * H * W) * 3 * sizeof(float));
-    return w;
+    lsr::Carver c(base);
+    a.partial = c.take<double>((size_t)(V * C * tiles) * 3);
+    a.maps = c.take<float>((size_t)(V * C * H * W) * 3);
+    return c.total();
 }
 
 bool sizes_ok(int32_t V, int32_t C, int32_t H, int32_t W) {
@@ -311,7 +297,7 @@ int image_loss_args(const std::string& what, int32_t V, int32_t C, int32_t H, in
     if (gt_view_stride < (int64_t)C * H * W && V > 1)
         return lsr::fail(LSR_EINVAL, what + ": gt_view_stride >= C H W required");
     if (!workspace) return lsr::fail(LSR_EINVAL, what + ": workspace required");
-    if (reinterpret_cast<uintptr_t>(workspace) & 15u)
+    if (!lsr::aligned16(workspace))
         return lsr::fail(LSR_EINVAL, what + ": the workspace must be 16-byte aligned");
     a = ImageLossArgs{};
     for (int v = 0; v < V; ++v) {
@@ -323,16 +309,8 @@ int image_loss_args(const std::string& what, int32_t V, int32_t C, int32_t H, in
     a.V = V; a.C = C; a.H = H; a.W = W;
     a.tiles_x = (W + IL_TW - 1) / IL_TW;
     a.tiles_y = (H + IL_TH - 1) / IL_TH;
-    const ImageLossWs w = carve(const_cast<void*>(workspace), V, C, H, W);
-    a.partial = w.partial;
-    a.maps = w.maps;
+    carve(a, const_cast<void*>(workspace), V, C, H, W);
     a.map_stride = (int64_t)V * C * H * W;
-    return LSR_OK;
-}
-
-int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lsr::fail(LSR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
     return LSR_OK;
 }
 
@@ -345,7 +323,8 @@ int64_t lsr_image_loss_workspace_bytes(int32_t V, int32_t C, int32_t H, int32_t 
         lsr::fail(LSR_EINVAL, "lsr_image_loss_workspace_bytes: 1 <= V <= 8, C, H, W >= 1 and V C <= 65535 required");
         return -1;
     }
-    return (int64_t)carve(nullptr, V, C, H, W).bytes;
+    ImageLossArgs a{};
+    return (int64_t)carve(a, nullptr, V, C, H, W);
 }
 
 int lsr_image_loss_views(int32_t V, int32_t C, int32_t H, int32_t W, const float* const* images, const float* gt,

@@ -22,11 +22,8 @@
 #include "../../include/lsr.h"
 #include "../../include/lsr_knn.h"
 #include "lsr_common.h"
+#include "lsr_host.h"
 #include "lsr_internal.h"
-
-namespace lsr {
-int fail(int code, const std::string& msg);   // lsr_api.hip (thread-local lsr_last_error)
-}
 
 namespace {
 
@@ -37,8 +34,6 @@ constexpr int KNN_BOX_CHUNK = 1024; // box bounds staged in LDS per round (24 KB
 struct Bounds {
     float mnx, mny, mnz, mxx, mxy, mxz;
 };
-
-size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
 struct KnnWs {
     Bounds* partial;      // [KNN_RED_BLOCKS]
@@ -51,20 +46,18 @@ struct KnnWs {
 };
 
 KnnWs carve(void* base, size_t P) {
-    char* b = static_cast<char*>(base);
+    lsr::Carver c(base);
     KnnWs w{};
-    size_t o = 0;
-    auto take = [&](size_t n) { char* p = b ? b + o : nullptr; o += al256(n); return p; };
-    w.partial = reinterpret_cast<Bounds*>(take(sizeof(Bounds) * KNN_RED_BLOCKS));
-    w.bbox = reinterpret_cast<Bounds*>(take(sizeof(Bounds)));
-    w.code_a = reinterpret_cast<uint32_t*>(take(4 * P));
-    w.code_b = reinterpret_cast<uint32_t*>(take(4 * P));
-    w.idx_a = reinterpret_cast<uint32_t*>(take(4 * P));
-    w.idx_b = reinterpret_cast<uint32_t*>(take(4 * P));
-    w.sort_tmp = take(lsr::radix_temp_bytes(P));
-    w.sp = reinterpret_cast<float4*>(take(sizeof(float4) * P));
-    w.boxes = reinterpret_cast<Bounds*>(take(sizeof(Bounds) * ((P + KNN_BOX - 1) / KNN_BOX)));
-    w.bytes = o;
+    w.partial = c.take<Bounds>(KNN_RED_BLOCKS);
+    w.bbox = c.take<Bounds>(1);
+    w.code_a = c.take<uint32_t>(P);
+    w.code_b = c.take<uint32_t>(P);
+    w.idx_a = c.take<uint32_t>(P);
+    w.idx_b = c.take<uint32_t>(P);
+    w.sort_tmp = c.take<char>(lsr::radix_temp_bytes(P));
+    w.sp = c.take<float4>(P);
+    w.boxes = c.take<Bounds>((P + KNN_BOX - 1) / KNN_BOX);
+    w.bytes = c.total();
     return w;
 }
 
@@ -230,9 +223,7 @@ int lsr_knn_mean_dist(int32_t P, const float* points, float* mean_dist, void* wo
     hipLaunchKernelGGL(k_box_bounds, dim3(nbox), dim3(256), 0, st, P, (const float4*)w.sp, w.boxes);
     hipLaunchKernelGGL(k_mean_dist, dim3(nblk), dim3(256), 0, st, P, nbox, (const float4*)w.sp, idx,
                        (const Bounds*)w.boxes, mean_dist);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lsr::fail(LSR_EHIP, std::string("knn: ") + hipGetErrorString(e));
-    return LSR_OK;
+    return lsr::launched("knn");
 }
 
 }  // extern "C"

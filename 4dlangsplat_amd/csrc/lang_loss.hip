@@ -17,12 +17,14 @@
 
 #include "../../include/lsr.h"
 #include "../../include/lsr_train.h"
-
-namespace lsr {
-int fail(int code, const std::string& msg);   // lsr_api.hip (thread-local lsr_last_error)
-}
+#include "lsr_host.h"
+#include "lsr_wave.h"
 
 namespace {
+
+using lsr::aligned16;
+using lsr::launched;
+using lsr::wave_sum;
 
 constexpr int SL_MAX_VIEWS = 8, SL_THREADS = 256, SL_WAVES = SL_THREADS / 64;
 constexpr int SL_SEG_LDS = 4096;     // labels of one row kept in LDS (16 KB); wider rows re-read the map
@@ -43,9 +45,6 @@ struct SegLossArgs {
     float* row_cos;    // [V][C][H][3]  (a.b, |a|^2, |b|^2) over w
     float* loss;
 };
-
-size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 __device__ __forceinline__ int checked_label(int s, int n_seg) { return (unsigned)s < (unsigned)n_seg ? s : -1; }
 
@@ -88,18 +87,6 @@ struct FwdAcc {
         }
     }
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 template <bool VEC, bool COS>
 __global__ void __launch_bounds__(SL_THREADS) k_seg_fwd(SegLossArgs a) {
@@ -240,19 +227,12 @@ __global__ void __launch_bounds__(SL_THREADS) k_seg_bwd(SegLossArgs a) {
     }
 }
 
-struct SegWs {
-    double* row_l1;
-    float* row_cos;
-    size_t bytes;
-};
-SegWs carve(void* base, int64_t V, int64_t C, int64_t H) {
-    char* b = static_cast<char*>(base);
-    SegWs w{};
-    const size_t l1 = al256((size_t)(V * H) * sizeof(double));
-    w.row_l1 = reinterpret_cast<double*>(b);
-    w.row_cos = reinterpret_cast<float*>(b ? b + l1 : nullptr);
-    w.bytes = l1 + al256((size_t)(V * C * H) * 3 * sizeof(float));
-    return w;
+// the workspace carved into a's row sums; returns its bytes
+size_t carve(SegLossArgs& a, void* base, int64_t V, int64_t C, int64_t H) {
+    lsr::Carver c(base);
+    a.row_l1 = c.take<double>((size_t)(V * H));
+    a.row_cos = c.take<float>((size_t)(V * C * H) * 3);
+    return c.total();
 }
 
 bool sizes_ok(int32_t V, int32_t C, int32_t H, int32_t W) {
@@ -265,7 +245,7 @@ int seg_args(const std::string& what, int32_t V, int32_t C, int32_t H, int32_t W
     if (!sizes_ok(V, C, H, W)) return lsr::fail(LSR_EINVAL, what + ": 1 <= V <= 8 and C, H, W >= 1 required");
     if (!views) return lsr::fail(LSR_EINVAL, what + ": views required");
     if (need_ws && !workspace) return lsr::fail(LSR_EINVAL, what + ": workspace required");
-    if (need_ws && !al16(workspace)) return lsr::fail(LSR_EINVAL, what + ": the workspace must be 16-byte aligned");
+    if (need_ws && !aligned16(workspace)) return lsr::fail(LSR_EINVAL, what + ": the workspace must be 16-byte aligned");
     a = SegLossArgs{};
     vec = W % 4 == 0;
     for (int v = 0; v < V; ++v) {
@@ -278,19 +258,11 @@ int seg_args(const std::string& what, int32_t V, int32_t C, int32_t H, int32_t W
         a.seg[v] = s.seg;
         a.table[v] = s.table;
         a.n_seg[v] = s.n_seg;
-        vec = vec && al16(s.image) && al16(s.seg) && (!backward || al16(s.d_image));
+        vec = vec && aligned16(s.image) && aligned16(s.seg) && (!backward || aligned16(s.d_image));
     }
     a.V = V; a.C = C; a.H = H; a.W = W;
     a.lam = lam; a.beta = beta;
-    const SegWs w = carve(workspace, V, C, H);
-    a.row_l1 = w.row_l1;
-    a.row_cos = w.row_cos;
-    return LSR_OK;
-}
-
-int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lsr::fail(LSR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+    carve(a, workspace, V, C, H);
     return LSR_OK;
 }
 
@@ -303,7 +275,8 @@ int64_t lsr_seg_loss_workspace_bytes(int32_t V, int32_t C, int32_t H, int32_t W)
         lsr::fail(LSR_EINVAL, "lsr_seg_loss_workspace_bytes: 1 <= V <= 8 and C, H, W >= 1 required");
         return -1;
     }
-    return (int64_t)carve(nullptr, V, C, H).bytes;
+    SegLossArgs a{};
+    return (int64_t)carve(a, nullptr, V, C, H);
 }
 
 int lsr_seg_loss_views(int32_t V, int32_t C, int32_t H, int32_t W, const lsr_seg_view* views, float lam, float beta,

@@ -5,7 +5,6 @@
 // Backward = composite backward (per-Gaussian screen-space sums) -> preprocess backward.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -14,29 +13,38 @@
 
 #include "../../include/lsr.h"
 #include "lsr_common.h"
+#include "lsr_host.h"
 #include "lsr_internal.h"
 
 namespace {
+thread_local std::string g_err;   // lsr_last_error
+}
 
-thread_local std::string g_err;
-std::atomic<int32_t> g_caller_api{0};   // lsr_require_api: the lsr.h version the caller was built against
-
-int fail(int code, const std::string& msg) {
+// the library's one error path (lsr_host.h): every unit reports through it
+int lsr::fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
 
-#define LSR_HIP(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) return fail(LSR_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+namespace {
+
+using lsr::Carver;
+using lsr::fail;
+
+// lsr_require_api: the lsr.h version the caller was built against
+lsr::ApiGate g_api{"lsr", "LSR_API_VERSION", LSR_API_VERSION, "lsr.h version " + std::to_string(LSR_API_VERSION)};
+
+#define LSR_HIP(expr)                                                  \
+    do {                                                               \
+        if (int rc_ = lsr::launched(#expr, (expr))) return rc_;        \
     } while (0)
 
-#define LSR_LAUNCHED(name, st, debug)                                                        \
-    do {                                                                                     \
-        hipError_t e_ = hipGetLastError();                                                   \
-        if (e_ == hipSuccess && (debug)) e_ = hipStreamSynchronize(st);                      \
-        if (e_ != hipSuccess) return fail(LSR_EHIP, std::string(name) + ": " + hipGetErrorString(e_)); \
+// after a launch; debug: wait for the kernels too, so that a fault is reported by the phase that caused it
+#define LSR_LAUNCHED(name, st, debug)                                   \
+    do {                                                                \
+        hipError_t e_ = hipGetLastError();                              \
+        if (e_ == hipSuccess && (debug)) e_ = hipStreamSynchronize(st); \
+        if (int rc_ = lsr::launched(name, e_)) return rc_;              \
     } while (0)
 
 // ---- per-phase event timing (lsr_profile_*) ----------------------------------------------------
@@ -74,22 +82,6 @@ struct PhaseTimer {
         (void)hipEventRecord(b, st);
         std::lock_guard<std::mutex> l(g_prof.mu);
         g_prof.pending.push_back({phase, a, b});
-    }
-};
-
-constexpr size_t kAlign = 256;
-inline size_t al(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
-
-// Bump allocator over a caller-owned workspace; the same carve order gives the size query.
-struct Carver {
-    char* base;
-    size_t off = 0;
-    explicit Carver(void* b) : base(static_cast<char*>(b)) {}
-    template <typename T>
-    T* take(size_t n) {
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += al(n * sizeof(T));
-        return p;
     }
 };
 
@@ -134,7 +126,7 @@ Geom carve_geom(void* base, size_t P, size_t* bytes) {
     g.sort_tmp = c.take<char>(lsr::radix_temp_bytes(P));
     g.scan_tmp = c.take<char>(lsr::scan_temp_bytes(P));
     g.acc = c.take<float4>(P * (lsr::ACC_PITCH / 4));
-    if (bytes) *bytes = c.off;
+    if (bytes) *bytes = c.total();
     return g;
 }
 
@@ -152,12 +144,12 @@ Binning carve_binning(void* base, size_t K, size_t* bytes) {
     b.val_b = c.take<uint32_t>(K);
     b.sort_tmp = c.take<char>(lsr::radix_temp_bytes(K));
     b.kept = c.take<uint32_t>(4);
-    if (bytes) *bytes = c.off;
+    if (bytes) *bytes = c.total();
     return b;
 }
 
 // the tile-bucket binning's workspace: the sort path's layout (its point list buffer is where the
-// compositors read; key_a..key_b hold the 64-bit bucket keys: 8K bytes <= 2 al(4K)), then the
+// compositors read; key_a..key_b hold the 64-bit bucket keys: 8K bytes <= 2 align256(4K)), then the
 // per-block tile count table and the long buckets' merge workspace
 struct BinningTb {
     Binning b;
@@ -172,7 +164,7 @@ BinningTb carve_binning_tb(void* base, size_t K, size_t P, size_t ntiles, size_t
     c.off = head;
     t.table = c.take<uint32_t>((size_t)lsr::tb_blocks((int)P) * ntiles);
     t.tmp = c.take<uint64_t>(K);
-    if (bytes) *bytes = c.off;
+    if (bytes) *bytes = c.total();
     return t;
 }
 
@@ -198,7 +190,7 @@ Img carve_img(void* base, int W, int H, size_t* bytes) {
     m.final_T = c.take<float>((size_t)W * H);
     m.n_contrib = c.take<uint32_t>((size_t)W * H);
     m.tile_order = c.take<uint32_t>(ntiles);
-    if (bytes) *bytes = c.off;
+    if (bytes) *bytes = c.total();
     return m;
 }
 
@@ -216,7 +208,7 @@ Scratch carve_scratch(void* base, size_t P, size_t K, int recq, bool det, size_t
     } else {
         s.acc_small = c.take<float>(P * lsr::ACC_PITCH);
     }
-    if (bytes) *bytes = c.off;
+    if (bytes) *bytes = c.total();
     return s;
 }
 
@@ -233,9 +225,7 @@ uint32_t* point_list(const Binning& b, Grid grid) { return tile_sort_in_b((int)g
 int depth_sort_result_in_b() { return 0; }  // 4 passes, or 3 planned on the device: either way in the (a) buffers
 
 int check_common(const lsr_settings* s, const lsr_fwd_in* in) {
-    if (g_caller_api.load() != LSR_API_VERSION)   // the structs' layout is that of this lsr.h only
-        return fail(LSR_EINVAL, "call lsr_require_api(LSR_API_VERSION) first: the caller must be built against lsr.h "
-                                "version " + std::to_string(LSR_API_VERSION));
+    if (int rc = g_api.check()) return rc;   // the structs' layout is that of this lsr.h only
     if (!s || !in) return fail(LSR_EINVAL, "null settings or inputs");
     if (s->image_width <= 0 || s->image_height <= 0) return fail(LSR_EINVAL, "image size must be positive");
     if (s->image_width > 4095 * LSR_TILE_X || s->image_height > 4095 * LSR_TILE_Y)
@@ -602,13 +592,7 @@ void view_cam(lsr::ViewCam& c, const lsr_settings* s, const Geom& g, const float
 extern "C" {
 
 int lsr_version(void) { return LSR_API_VERSION; }
-int lsr_require_api(int32_t caller_version) {
-    if (caller_version != LSR_API_VERSION)
-        return fail(LSR_EINVAL, "lsr.h version mismatch: caller " + std::to_string(caller_version) + ", library " +
-                                    std::to_string(LSR_API_VERSION));
-    g_caller_api.store(caller_version);
-    return LSR_OK;
-}
+int lsr_require_api(int32_t caller_version) { return g_api.require(caller_version); }
 const char* lsr_last_error(void) { return g_err.c_str(); }
 
 int64_t lsr_geom_bytes(int32_t P) {
@@ -1027,9 +1011,9 @@ int lsr_radii_max(int32_t P, int32_t n_views, const int32_t* const* radii, int32
                   lsr_stream_t stream) {
     if (P < 0 || n_views < 0 || (P > 0 && n_views > 0 && (!radii || !out))) return fail(LSR_EINVAL, "bad lsr_radii_max arguments");
     for (int v = 0; v < n_views; ++v)
-        if (P > 0 && (!radii[v] || (reinterpret_cast<uintptr_t>(radii[v]) & 15)))
+        if (P > 0 && (!radii[v] || !lsr::aligned16(radii[v])))
             return fail(LSR_EINVAL, "lsr_radii_max: every radii array must be a 16-byte aligned device pointer");
-    if (P > 0 && (reinterpret_cast<uintptr_t>(out) & 15)) return fail(LSR_EINVAL, "lsr_radii_max: out must be 16-byte aligned");
+    if (P > 0 && !lsr::aligned16(out)) return fail(LSR_EINVAL, "lsr_radii_max: out must be 16-byte aligned");
     if (P == 0 || n_views == 0) return LSR_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     lsr::launch_radii_max(P, n_views, reinterpret_cast<const int* const*>(radii), out, accumulate != 0, st);
@@ -1087,8 +1071,3 @@ int lsr_profile_read(double* ms_total, int64_t* launches, int32_t n) {
 }
 
 }  // extern "C"
-
-namespace lsr {
-// shared with the other C-ABI translation units (deform_api.hip)
-int fail(int code, const std::string& msg) { return ::fail(code, msg); }
-}  // namespace lsr

@@ -40,18 +40,14 @@
 
 #include "../../include/lsr.h"
 #include "../../include/lsr_pca.h"
+#include "lsr_host.h"
 #include "lsr_mfma.h"
-
-namespace lsr {
-int fail(int code, const std::string& msg);   // lsr_api.hip (thread-local lsr_last_error)
-}
+#include "lsr_wave.h"
 
 namespace {
 
 using lsr::f32x4;
-
-#define LSR_LDS __attribute__((address_space(3)))
-typedef LSR_LDS float lds_float;
+using lsr::lds_float;
 
 constexpr int PCA_THREADS = 256, PCA_WAVES = PCA_THREADS / 64;
 constexpr int PCA_TILE = LSR_PCA_TILE_PIXELS;          // pixels staged at once: 64 per wave
@@ -512,7 +508,7 @@ k_pca_colorize(int64_t n, const float* __restrict__ y, const float* __restrict__
 // vec: a whole tile can be fetched 16 bytes at a time, as channel rows of contiguous pixels or as
 // contiguous pixels of C channels
 Frame frame_of(const float* x, int64_t n_pix, int64_t pix_stride, int64_t chan_stride, int C) {
-    const bool aligned = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+    const bool aligned = lsr::aligned16(x);
     const bool rows = pix_stride == 1 && chan_stride != 1 && chan_stride % 4 == 0;
     const bool packed = chan_stride == 1 && pix_stride == C && C % 4 == 0;
     return Frame{x, n_pix, pix_stride, chan_stride, C, aligned && (rows || packed) ? 1 : 0};
@@ -535,11 +531,6 @@ int check_sweep(const char* what, int32_t C, int64_t n_pix, const void* frame, i
         return lsr::fail(LSR_EINVAL, std::string(what) + ": workspace must be 8-byte aligned");
     *blocks = block_count(n_pix);
     if (*blocks > 0x7fffffffLL) return lsr::fail(LSR_EINVAL, std::string(what) + ": n_pix too large for one launch");
-    return LSR_OK;
-}
-
-int launched(const char* what) {
-    if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, std::string(what) + " launch failed");
     return LSR_OK;
 }
 
@@ -566,7 +557,7 @@ extern "C" int lsr_pca_sums(int32_t C, int64_t n_pix, const float* frame, int64_
     const Frame f = frame_of(frame, n_pix, pix_stride, chan_stride, C);
     hipLaunchKernelGGL(k_pca_sums, dim3((unsigned)blocks), dim3(PCA_THREADS), 0, st, f, static_cast<double*>(workspace));
     hipLaunchKernelGGL(k_pca_finish<false>, dim3(1), dim3(64 * PCA_FINISH_WAVES), 0, st, (const void*)workspace, blocks, (int)reset, sums);
-    return launched("lsr_pca_sums");
+    return lsr::launched("lsr_pca_sums launch failed");
 }
 
 extern "C" int lsr_pca_gram(int32_t C, int64_t n_pix, const float* frame, int64_t pix_stride, int64_t chan_stride,
@@ -583,7 +574,7 @@ extern "C" int lsr_pca_gram(int32_t C, int64_t n_pix, const float* frame, int64_
     hipLaunchKernelGGL(k_pca_gram, dim3((unsigned)blocks), dim3(PCA_THREADS), 0, st, f, sums, (double)n_total,
                        static_cast<float*>(workspace));
     hipLaunchKernelGGL(k_pca_finish<true>, dim3(PCA_GRAM_PARTIAL / 64), dim3(64 * PCA_FINISH_WAVES), 0, st, (const void*)workspace, blocks, (int)reset, gram);
-    return launched("lsr_pca_gram");
+    return lsr::launched("lsr_pca_gram launch failed");
 }
 
 extern "C" int lsr_pca_basis(int32_t C, int64_t n_total, const double* sums, const double* gram, float* mean,
@@ -596,7 +587,7 @@ extern "C" int lsr_pca_basis(int32_t C, int64_t n_total, const double* sums, con
         return lsr::fail(LSR_EINVAL, "lsr_pca_basis: sums, gram, mean, components and eigenvalues are required");
     hipLaunchKernelGGL(k_pca_basis, dim3(1), dim3(PCA_BASIS_THREADS), 0, reinterpret_cast<hipStream_t>(stream), (int)C,
                        (double)n_total, sums, gram, mean, components, eigenvalues);
-    return launched("lsr_pca_basis");
+    return lsr::launched("lsr_pca_basis launch failed");
 }
 
 extern "C" int lsr_pca_project(int32_t C, int64_t n_pix, const float* frame, int64_t pix_stride, int64_t chan_stride,
@@ -616,7 +607,7 @@ extern "C" int lsr_pca_project(int32_t C, int64_t n_pix, const float* frame, int
     if (range)
         hipLaunchKernelGGL(k_pca_range, dim3(1), dim3(PCA_THREADS), 0, st, (const float*)workspace, blocks, (int)reset,
                            range);
-    return launched("lsr_pca_project");
+    return lsr::launched("lsr_pca_project launch failed");
 }
 
 namespace {
@@ -629,7 +620,7 @@ int colorize(const char* what, int64_t n_pix, const float* y, const float* range
     if (blocks == 0) return LSR_OK;
     hipLaunchKernelGGL(k_pca_colorize<BYTES>, dim3((unsigned)blocks), dim3(PCA_THREADS), 0,
                        reinterpret_cast<hipStream_t>(stream), n, y, range, out);
-    return launched(what);
+    return lsr::launched(std::string(what) + " launch failed");
 }
 }  // namespace
 

@@ -24,12 +24,12 @@
 
 #include "../../include/lsr.h"
 #include "../../include/lsr_plane_reg.h"
-
-namespace lsr {
-int fail(int code, const std::string& msg);   // lsr_api.hip (thread-local lsr_last_error)
-}
+#include "lsr_host.h"
+#include "lsr_wave.h"
 
 namespace {
+
+using lsr::wave_sum;
 
 constexpr int PR_MAX = LSR_PLANE_REG_MAX_PLANES;
 constexpr int PR_BLOCK = LSR_PLANE_REG_BLOCK_ELEMS;     // elements of one block
@@ -54,12 +54,6 @@ struct Args {
     int32_t n_planes, accumulate;
 };
 static_assert(sizeof(Args) <= 4096, "the descriptors travel as kernel arguments");
-
-// the sum over the wave, in every lane: a fixed tree
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __global__ void __launch_bounds__(PR_THREADS) k_plane_reg(const Args a, double* __restrict__ partial) {
     __shared__ double red[2][PR_WAVES];
@@ -202,6 +196,5 @@ extern "C" int lsr_plane_reg(int32_t n_planes, const lsr_plane_desc* planes, int
         hipLaunchKernelGGL(k_plane_reg, dim3((unsigned)blocks), dim3(PR_THREADS), 0, st, a, static_cast<double*>(workspace));
     hipLaunchKernelGGL(k_plane_reg_finish, dim3(1), dim3(64 * PR_FINISH_WAVES), 0, st, a,
                        static_cast<const double*>(workspace), terms, total, total64);
-    if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "lsr_plane_reg launch failed");
-    return LSR_OK;
+    return lsr::launched("lsr_plane_reg launch failed");
 }

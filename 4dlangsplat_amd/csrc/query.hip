@@ -26,19 +26,19 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdint>
 #include <string>
 
 #include "../../include/lsr.h"
 #include "../../include/lsr_query.h"
+#include "lsr_host.h"
 #include "lsr_mfma.h"
-
-namespace lsr {
-int fail(int code, const std::string& msg);   // lsr_api.hip (thread-local lsr_last_error)
-}
+#include "lsr_wave.h"
 
 namespace {
+
+using lsr::aligned16;
+using lsr::lds_float;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -62,11 +62,8 @@ struct QueryArgs {
     int32_t vec_ok;      // bit i: weight[i] rows can be fetched 16 bytes at a time; bit 8 / 9: pos / neg
 };
 
-// LDS pointers carry their address space: through a generic pointer the activation reads become flat
-// loads, whose wait (vmcnt and lgkmcnt) also waits for the weight prefetch in flight
-#define LSR_LDS __attribute__((address_space(3)))
-typedef LSR_LDS float lds_float;
-
+// (the activation images are read through lds_float: through a generic pointer the reads would be flat
+// loads, whose wait also waits for the weight prefetch in flight)
 template <int NPT> struct PixVec;
 template <> struct PixVec<4> { typedef f32x4 type; typedef LSR_LDS f32x4 lds_type; };
 template <> struct PixVec<2> { typedef f32x2 type; typedef LSR_LDS f32x2 lds_type; };
@@ -341,14 +338,10 @@ k_query(const QueryArgs a) {
     }
 }
 
-std::atomic<int> g_query_caller_api{0};
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+lsr::ApiGate g_query_api{"lsr_query", "LSR_QUERY_API_VERSION", LSR_QUERY_API_VERSION, "this library's lsr_query.h"};
 
 int check_decoder(const lsr_decoder* d) {
-    if (g_query_caller_api.load() != LSR_QUERY_API_VERSION)
-        return lsr::fail(LSR_EINVAL, "call lsr_query_require_api(LSR_QUERY_API_VERSION) first: the caller must be "
-                                     "built against this library's lsr_query.h");
+    if (int rc = g_query_api.check()) return rc;
     if (!d) return lsr::fail(LSR_EINVAL, "null decoder");
     if (d->n_layers < 1 || d->n_layers > LSR_QUERY_MAX_LAYERS)
         return lsr::fail(LSR_EINVAL, "n_layers must be in [1, " + std::to_string(LSR_QUERY_MAX_LAYERS) + "]");
@@ -399,19 +392,12 @@ int launch(QueryArgs& a, hipStream_t st) {
                             (int)lds) != hipSuccess)
         return lsr::fail(LSR_EHIP, "query: cannot reserve the activation image in LDS");
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kThreads), lds, st, a);
-    if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "query launch failed");
-    return LSR_OK;
+    return lsr::launched("query launch failed");
 }
 
 }  // namespace
 
-extern "C" int lsr_query_require_api(int32_t caller_version) {
-    if (caller_version != LSR_QUERY_API_VERSION)
-        return lsr::fail(LSR_EINVAL, "lsr_query.h version mismatch: caller " + std::to_string(caller_version) +
-                                         ", library " + std::to_string(LSR_QUERY_API_VERSION));
-    g_query_caller_api.store(caller_version);
-    return LSR_OK;
-}
+extern "C" int lsr_query_require_api(int32_t caller_version) { return g_query_api.require(caller_version); }
 
 extern "C" int lsr_query_relevancy(const lsr_decoder* dec, int64_t n_pix, const float* latent, int64_t pix_stride,
                                    int64_t chan_stride, int32_t n_pos, const float* pos_embeds, int32_t n_neg,

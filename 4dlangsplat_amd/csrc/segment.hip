@@ -22,16 +22,14 @@
 
 #include "../../include/lsr.h"
 #include "../../include/lsr_segment.h"
-
-namespace lsr {
-int fail(int code, const std::string& msg);   // lsr_api.hip (thread-local lsr_last_error)
-}
+#include "lsr_host.h"
+#include "lsr_wave.h"
 
 namespace {
 
-#define LSR_LDS __attribute__((address_space(3)))
-typedef LSR_LDS float lds_float;
-typedef LSR_LDS uint8_t lds_byte;
+using lsr::lds_byte;
+using lsr::lds_float;
+using lsr::wave_sum;
 
 constexpr int SG_THREADS = 256, SG_WAVES = SG_THREADS / 64;
 constexpr int SG_TW = 64;             // tile width: one wave per tile row
@@ -61,7 +59,6 @@ struct SegArgs {
     int* tile_cnt;
 };
 
-size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // LDS of one k_seg_blend block: the halo tile and its row sums
@@ -194,18 +191,6 @@ __global__ void __launch_bounds__(SG_THREADS) k_seg_minmax(SegArgs a, int m0) {
             a.uni[m] = 0ull;
         }
     }
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
 }
 
 __global__ void __launch_bounds__(SG_THREADS) k_seg_mask(SegArgs a, int m0) {
@@ -347,7 +332,7 @@ __global__ void __launch_bounds__(SG_THREADS) k_seg_mean(SegArgs a, int m0) {
     }
     sum = wave_sum(sum);
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off);
+    for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off);   // (as wave_sum<long long> the kernel's code differs)
     if ((tid & 63) == 0) {
         s_d[tid >> 6] = sum;
         s_c[tid >> 6] = cnt;
@@ -364,32 +349,19 @@ bool sizes_ok(int32_t n_maps, int32_t H, int32_t W) {
     return n_maps >= 0 && H >= 1 && H <= LSR_SEGMENT_MAX_SIDE && W >= 1 && W <= LSR_SEGMENT_MAX_SIDE;
 }
 
-// The workspace for any scale: k_seg_blend's tile count is bounded by its small tile height.
-struct SegWs {
-    float *tile_min, *tile_max, *map_min, *map_max;
-    double* tile_sum;
-    int* tile_cnt;
-    size_t bytes;
-};
-SegWs carve(void* base, int64_t n_maps, int H, int W) {
+// The workspace for any scale (k_seg_blend's tile count is bounded by its small tile height), carved
+// into a's pointers; returns its bytes.
+size_t carve(SegArgs& a, void* base, int64_t n_maps, int H, int W) {
     const size_t tiles_x = cdiv(W, SG_TW);
     const size_t nb = (size_t)n_maps * tiles_x * cdiv(H, SG_TH_SMALL), nm = (size_t)n_maps * tiles_x * cdiv(H, SG_TH);
-    char* b = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = b ? b + off : nullptr;
-        off += al256(bytes);
-        return p;
-    };
-    SegWs w{};
-    w.tile_sum = reinterpret_cast<double*>(take(nm * sizeof(double)));
-    w.tile_min = reinterpret_cast<float*>(take(nb * sizeof(float)));
-    w.tile_max = reinterpret_cast<float*>(take(nb * sizeof(float)));
-    w.map_min = reinterpret_cast<float*>(take((size_t)n_maps * sizeof(float)));
-    w.map_max = reinterpret_cast<float*>(take((size_t)n_maps * sizeof(float)));
-    w.tile_cnt = reinterpret_cast<int*>(take(nm * sizeof(int)));
-    w.bytes = off;
-    return w;
+    lsr::Carver c(base);
+    a.tile_sum = c.take<double>(nm);
+    a.tile_min = c.take<float>(nb);
+    a.tile_max = c.take<float>(nb);
+    a.map_min = c.take<float>((size_t)n_maps);
+    a.map_max = c.take<float>((size_t)n_maps);
+    a.tile_cnt = c.take<int>(nm);
+    return c.total();
 }
 
 }  // namespace
@@ -401,7 +373,8 @@ int64_t lsr_segment_workspace_bytes(int32_t n_maps, int32_t H, int32_t W) {
         lsr::fail(LSR_EINVAL, "lsr_segment_workspace_bytes: n_maps >= 0 and 1 <= H, W <= 16384 required");
         return -1;
     }
-    return (int64_t)carve(nullptr, n_maps, H, W).bytes;
+    SegArgs a{};
+    return (int64_t)carve(a, nullptr, n_maps, H, W);
 }
 
 int lsr_segment(int32_t n_maps, int32_t H, int32_t W, const float* rel, int32_t scale, float thresh, int32_t strategy,
@@ -420,7 +393,7 @@ int lsr_segment(int32_t n_maps, int32_t H, int32_t W, const float* rel, int32_t 
     if (!rel || !blended || !mask_raw || !mask || !score)
         return lsr::fail(LSR_EINVAL, what + ": null rel, blended, mask_raw, mask or score");
     if (!workspace) return lsr::fail(LSR_EINVAL, what + ": workspace required");
-    if (reinterpret_cast<uintptr_t>(workspace) & 15u)
+    if (!lsr::aligned16(workspace))
         return lsr::fail(LSR_EINVAL, what + ": the workspace must be 16-byte aligned");
 
     SegArgs a{};
@@ -442,13 +415,7 @@ int lsr_segment(int32_t n_maps, int32_t H, int32_t W, const float* rel, int32_t 
     a.gt_count = gt ? gt_count : 1;
     a.strategy = strategy;
     a.thresh = thresh;
-    const SegWs w = carve(workspace, n_maps, H, W);
-    a.tile_min = w.tile_min;
-    a.tile_max = w.tile_max;
-    a.map_min = w.map_min;
-    a.map_max = w.map_max;
-    a.tile_sum = w.tile_sum;
-    a.tile_cnt = w.tile_cnt;
+    carve(a, workspace, n_maps, H, W);
 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const size_t lds = blend_lds(a.r, a.th);
@@ -459,9 +426,7 @@ int lsr_segment(int32_t n_maps, int32_t H, int32_t W, const float* rel, int32_t 
         hipLaunchKernelGGL(k_seg_mask, dim3(a.tiles_m, n), dim3(SG_THREADS), 0, st, a, m0);
         if (strategy == LSR_SEGMENT_MEAN) hipLaunchKernelGGL(k_seg_mean, dim3(n), dim3(SG_THREADS), 0, st, a, m0);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lsr::fail(LSR_EHIP, what + ": " + hipGetErrorString(e));
-    return LSR_OK;
+    return lsr::launched(what);
 }
 
 }  // extern "C"

@@ -14,15 +14,13 @@
 #include "../../include/lsr.h"
 #include "../../include/lsr_train.h"
 #include "lsr_common.h"
+#include "lsr_host.h"
 #include "lsr_internal.h"
-
-namespace lsr {
-int fail(int code, const std::string& msg);   // lsr_api.hip (thread-local lsr_last_error)
-}
 
 namespace {
 
-size_t al256(size_t x) { return (x + 255) / 256 * 256; }
+using lsr::aligned16;
+using lsr::launched;
 
 // ---------------------------------------------------------------------------------------------
 // Adam.  Blocks own chunks of ADAM_CHUNK floats of one group; group g owns chunks
@@ -365,27 +363,17 @@ struct TrainWs {
     size_t bytes;
 };
 TrainWs carve(void* base, size_t P) {
-    char* b = static_cast<char*>(base);
+    lsr::Carver c(base);
     TrainWs w{};
-    size_t o = 0;
-    auto take = [&](size_t n) { char* p = b ? b + o : nullptr; o += al256(n); return p; };
-    w.f0 = reinterpret_cast<uint32_t*>(take(4 * P));
-    w.f1 = reinterpret_cast<uint32_t*>(take(4 * P));
-    w.o0 = reinterpret_cast<uint32_t*>(take(4 * P));
-    w.o1 = reinterpret_cast<uint32_t*>(take(4 * P));
-    w.totals = reinterpret_cast<uint32_t*>(take(16));
-    w.scan_tmp = take(lsr::scan_temp_bytes(P));
-    w.bytes = o;
+    w.f0 = c.take<uint32_t>(P);
+    w.f1 = c.take<uint32_t>(P);
+    w.o0 = c.take<uint32_t>(P);
+    w.o1 = c.take<uint32_t>(P);
+    w.totals = c.take<uint32_t>(4);
+    w.scan_tmp = c.take<char>(lsr::scan_temp_bytes(P));
+    w.bytes = c.total();
     return w;
 }
-
-int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lsr::fail(LSR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-    return LSR_OK;
-}
-
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 
@@ -408,7 +396,7 @@ int lsr_adam_step(const lsr_adam_group* groups, int32_t n_groups, double beta1, 
         const double bc1 = 1.0 - std::pow(beta1, (double)g.step), bc2 = 1.0 - std::pow(beta2, (double)g.step);
         d.w1 = (float)(1.0 - beta1); d.b2 = (float)beta2; d.w2 = (float)(1.0 - beta2);
         d.bc2s = (float)std::sqrt(bc2); d.ss = (float)(-(g.lr / bc1)); d.eps = (float)eps;
-        d.vec = al16(g.param) && al16(g.grad) && al16(g.exp_avg) && al16(g.exp_avg_sq);
+        d.vec = aligned16(g.param) && aligned16(g.grad) && aligned16(g.exp_avg) && aligned16(g.exp_avg_sq);
         a.chunk0[a.ng] = chunks;
         chunks += (g.n + ADAM_CHUNK - 1) / ADAM_CHUNK;
         ++a.ng;
@@ -614,7 +602,7 @@ int lsr_activate(int32_t P, const float* raw_scales, const float* raw_rotations,
     if (P < 0) return lsr::fail(LSR_EINVAL, "lsr_activate: P >= 0");
     if ((raw_scales && !scales) || (raw_rotations && !rotations) || (raw_opacity && !opacity))
         return lsr::fail(LSR_EINVAL, "lsr_activate: every given input needs its output");
-    if (raw_rotations && (!al16(raw_rotations) || !al16(rotations)))
+    if (raw_rotations && (!aligned16(raw_rotations) || !aligned16(rotations)))
         return lsr::fail(LSR_EINVAL, "lsr_activate: rotation rows must be 16-byte aligned");
     if (P == 0) return LSR_OK;
     hipLaunchKernelGGL(k_activate, dim3((P + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), P,
@@ -628,7 +616,7 @@ int lsr_activate_backward(int32_t P, const float* scales, const float* raw_rotat
     if (P < 0) return lsr::fail(LSR_EINVAL, "lsr_activate_backward: P >= 0");
     if ((d_raw_scales && !scales) || (d_raw_rotations && !raw_rotations) || (d_raw_opacity && !opacity))
         return lsr::fail(LSR_EINVAL, "lsr_activate_backward: every requested gradient needs its forward values");
-    if (d_raw_rotations && (!al16(raw_rotations) || !al16(d_raw_rotations) || (d_rotations && !al16(d_rotations))))
+    if (d_raw_rotations && (!aligned16(raw_rotations) || !aligned16(d_raw_rotations) || (d_rotations && !aligned16(d_rotations))))
         return lsr::fail(LSR_EINVAL, "lsr_activate_backward: rotation rows must be 16-byte aligned");
     if (P == 0) return LSR_OK;
     hipLaunchKernelGGL(k_activate_bwd, dim3((P + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), P,

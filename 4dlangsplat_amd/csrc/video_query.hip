@@ -27,20 +27,18 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdint>
 #include <string>
 
 #include "../../include/lsr.h"
 #include "../../include/lsr_video.h"
+#include "lsr_host.h"
 #include "lsr_mfma.h"
-
-namespace lsr {
-int fail(int code, const std::string& msg);   // lsr_api.hip (thread-local lsr_last_error)
-}
+#include "lsr_wave.h"
 
 namespace {
 
+using lsr::aligned16;
 using lsr::f32x4;
 using lsr::mfma4;
 
@@ -227,7 +225,7 @@ __global__ void __launch_bounds__(256) k_video_segment_mean(const float* __restr
     const float* src = cosine + (int64_t)seg_query[s] * n_rows;
     double v = 0.0;
     for (int64_t i = lo + tid; i < hi; i += 256) v += (double)src[i];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    v = lsr::wave_sum(v);
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
     if (tid == 0) {
@@ -236,16 +234,9 @@ __global__ void __launch_bounds__(256) k_video_segment_mean(const float* __restr
     }
 }
 
-std::atomic<int> g_video_caller_api{0};
+lsr::ApiGate g_video_api{"lsr_video", "LSR_VIDEO_API_VERSION", LSR_VIDEO_API_VERSION, "this library's lsr_video.h"};
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-int check_api(const char* what) {
-    if (g_video_caller_api.load() != LSR_VIDEO_API_VERSION)
-        return lsr::fail(LSR_EINVAL, std::string(what) + ": call lsr_video_require_api(LSR_VIDEO_API_VERSION) first: the "
-                                     "caller must be built against this library's lsr_video.h");
-    return LSR_OK;
-}
+int check_api(const char* what) { return g_video_api.check(what); }
 
 // the checks the size query and the call share
 int check_shapes(const char* what, const lsr_decoder* d, int64_t n_rows) {
@@ -286,13 +277,7 @@ Layout layout_of(const lsr_decoder& d, int64_t n_rows) {
 
 }  // namespace
 
-extern "C" int lsr_video_require_api(int32_t caller_version) {
-    if (caller_version != LSR_VIDEO_API_VERSION)
-        return lsr::fail(LSR_EINVAL, "lsr_video.h version mismatch: caller " + std::to_string(caller_version) +
-                                         ", library " + std::to_string(LSR_VIDEO_API_VERSION));
-    g_video_caller_api.store(caller_version);
-    return LSR_OK;
-}
+extern "C" int lsr_video_require_api(int32_t caller_version) { return g_video_api.require(caller_version); }
 
 extern "C" int64_t lsr_video_workspace_bytes(const lsr_decoder* dec, int64_t n_rows) {
     if (int rc = check_shapes("lsr_video_workspace_bytes", dec, n_rows)) return -(int64_t)rc;
@@ -343,8 +328,7 @@ extern "C" int lsr_video_cosine(const lsr_decoder* dec, int64_t n_rows, const fl
     const int n_ct = (d.dims[d.n_layers] + VQ_BN - 1) / VQ_BN;
     hipLaunchKernelGGL(k_video_finish, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, partial, n_rows, n_ct,
                        (int)n_q, cosine);
-    if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "lsr_video_cosine launch failed");
-    return LSR_OK;
+    return lsr::launched("lsr_video_cosine launch failed");
 }
 
 extern "C" int lsr_video_segment_mean(int64_t n_rows, int32_t n_q, const float* cosine, int32_t n_seg,
@@ -359,6 +343,5 @@ extern "C" int lsr_video_segment_mean(int64_t n_rows, int32_t n_q, const float* 
     if (n_seg == 0) return LSR_OK;
     hipLaunchKernelGGL(k_video_segment_mean, dim3((unsigned)n_seg), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        cosine, n_rows, seg_offsets, seg_query, mean);
-    if (hipGetLastError() != hipSuccess) return lsr::fail(LSR_EHIP, "lsr_video_segment_mean launch failed");
-    return LSR_OK;
+    return lsr::launched("lsr_video_segment_mean launch failed");
 }
