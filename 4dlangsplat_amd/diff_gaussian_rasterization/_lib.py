@@ -17,6 +17,7 @@ API_VERSION = 4               # LSR_API_VERSION of the include/lsr.h these struc
 DEFORM_API_VERSION = 3        # LSR_DEFORM_API_VERSION of include/lsr_deform.h (DeformNet, DeformGrads)
 QUERY_API_VERSION = 1         # LSR_QUERY_API_VERSION of include/lsr_query.h (Decoder)
 VIDEO_API_VERSION = 1         # LSR_VIDEO_API_VERSION of include/lsr_video.h
+AE_API_VERSION = 1            # LSR_AE_API_VERSION of include/lsr_autoencoder.h (AeParams, Autoencoder)
 
 
 class Settings(ctypes.Structure):
@@ -103,6 +104,18 @@ class Decoder(ctypes.Structure):
                 ("bias", ctypes.c_void_p * 8)]
 
 
+class AeParams(ctypes.Structure):
+    """include/lsr_autoencoder.h lsr_ae_params"""
+    _fields_ = [(n, ctypes.c_void_p * 8) for n in ("enc_w", "enc_b", "bn_w", "bn_b", "dec_w", "dec_b")]
+
+
+class Autoencoder(ctypes.Structure):
+    """include/lsr_autoencoder.h lsr_autoencoder"""
+    _fields_ = [("n_enc", ctypes.c_int32), ("n_dec", ctypes.c_int32), ("feature_dim", ctypes.c_int32),
+                ("enc_dims", ctypes.c_int32 * 8), ("dec_dims", ctypes.c_int32 * 8), ("p", AeParams),
+                ("bn_mean", ctypes.c_void_p * 8), ("bn_var", ctypes.c_void_p * 8), ("bn_count", ctypes.c_void_p * 8)]
+
+
 class PlaneDesc(ctypes.Structure):
     """include/lsr_plane_reg.h lsr_plane_desc"""
     _fields_ = [("t", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("C", ctypes.c_int32), ("H", ctypes.c_int32),
@@ -135,6 +148,11 @@ VIDEO_MAX_WIDTH = 4096      # LSR_VIDEO_MAX_WIDTH (include/lsr_video.h)
 VIDEO_MAX_QUERIES = 16      # LSR_VIDEO_MAX_QUERIES
 VIDEO_ROW_TILE = 128        # LSR_VIDEO_ROW_TILE
 VIDEO_COL_TILE = 128        # LSR_VIDEO_COL_TILE
+AE_MAX_LAYERS = 8           # LSR_AE_MAX_LAYERS (include/lsr_autoencoder.h)
+AE_MAX_WIDTH = 4096         # LSR_AE_MAX_WIDTH
+AE_MAX_LATENT = 32          # LSR_AE_MAX_LATENT
+AE_MAX_BATCH = 64           # LSR_AE_MAX_BATCH
+AE_EVAL_CHUNK = 2048        # LSR_AE_EVAL_CHUNK
 
 _vp = ctypes.c_void_p
 SIGNATURES = {
@@ -298,6 +316,14 @@ SIGNATURES = {
     "lsr_video_cosine": (ctypes.c_int, [ctypes.POINTER(Decoder), ctypes.c_int64, _vp, ctypes.c_int32, _vp, _vp, _vp,
                                         ctypes.c_int64, _vp]),
     "lsr_video_segment_mean": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp]),
+    "lsr_ae_require_api": (ctypes.c_int, [ctypes.c_int32]),
+    "lsr_ae_workspace_size": (ctypes.c_int64, [ctypes.POINTER(Autoencoder), ctypes.c_int64, ctypes.c_int32]),
+    "lsr_ae_encode": (ctypes.c_int, [ctypes.POINTER(Autoencoder), ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64, _vp]),
+    "lsr_ae_eval_loss": (ctypes.c_int, [ctypes.POINTER(Autoencoder), ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64,
+                                        _vp]),
+    "lsr_ae_train_step": (ctypes.c_int, [ctypes.POINTER(Autoencoder), ctypes.POINTER(AeParams),
+                                         ctypes.POINTER(AeParams), ctypes.c_int32, _vp] + [ctypes.c_double] * 4
+                          + [ctypes.c_int64, ctypes.c_double, _vp, _vp, ctypes.c_int64, _vp]),
     "lsr_profile_read": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
                                         ctypes.c_int32]),
 }
@@ -339,7 +365,8 @@ def load():
             fn.argtypes = args
         if (lib.lsr_require_api(API_VERSION) != 0 or lib.lsr_deform_require_api(DEFORM_API_VERSION) != 0
                 or lib.lsr_query_require_api(QUERY_API_VERSION) != 0
-                or lib.lsr_video_require_api(VIDEO_API_VERSION) != 0):
+                or lib.lsr_video_require_api(VIDEO_API_VERSION) != 0
+                or lib.lsr_ae_require_api(AE_API_VERSION) != 0):
             raise ImportError(f"{path}: {lib.lsr_last_error().decode()} (rebuild it: make -C 4dlangsplat_amd/csrc)")
         _LIB = lib
     return _LIB
