@@ -8,7 +8,8 @@
 // the ReLU while it stages the operand (load_act), forward and backward alike.
 //
 // k_ae_fwd<EPI>     H = act(A) . W^T + b.  K runs in blocks of 32, global -> registers -> LDS (rows padded
-//                   to 36 floats), the next block's loads in flight while this one is multiplied.  The MFMA
+//                   to 36 floats), the next block's loads in flight while this one is multiplied: lsr_dense.h's
+//                   dense_k_loop, which k_ae_dx runs too and the video decoder's layers.  The MFMA
 //                   is a k-ordered fmaf chain: a chain ends after 4 k blocks (128 terms) and the chains are
 //                   added in order, which keeps the rounding of a 4096-term sum near a blocked sum's.
 //                     STATS  the layer feeds a BatchNorm in train mode: the slab's column mean and biased
@@ -40,19 +41,22 @@
 
 #include "../../include/lsr.h"
 #include "../../include/lsr_autoencoder.h"
+#include "lsr_dense.h"
 #include "lsr_host.h"
 #include "lsr_mfma.h"
 #include "lsr_wave.h"
 
 namespace {
 
-using lsr::aligned16;
 using lsr::f32x4;
+using lsr::load4;
 using lsr::mfma4;
+using lsr::rows_vec;
+using lsr::sum16;
 
-constexpr int AE_BM = 64, AE_BN = 32, AE_BK = 32;
-constexpr int AE_LDK = AE_BK + 4;                 // LDS row stride in floats (16-byte aligned rows)
-constexpr int AE_THREADS = 256;
+constexpr int AE_BM = 64, AE_BN = 32, AE_BK = lsr::DENSE_BK;
+constexpr int AE_LDK = lsr::DENSE_LDK;            // LDS row stride in floats (16-byte aligned rows)
+constexpr int AE_THREADS = lsr::DENSE_THREADS;
 constexpr int AE_CHAIN = 4;                       // k blocks of one fmaf chain of the layer kernels: 128 terms
 constexpr int AE_DW_BN = 64, AE_DW_LDN = AE_DW_BN + 4;   // k_ae_dw_adam: rows of W of one block
 constexpr int AE_L = LSR_AE_MAX_LAYERS;
@@ -92,21 +96,6 @@ __device__ __forceinline__ void adam(const Moments& t, int64_t i, float g, const
     t.p[i] = t.p[i] - h.step * (m / (sqrtf(v) / h.sqrt_bc2 + h.eps));
 }
 
-// X[row][k .. k + 3] of a [rows, K] matrix, zero outside it
-__device__ __forceinline__ f32x4 load4(const float* __restrict__ X, int64_t row, int64_t n_rows, int k, int K, bool vec) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (row >= n_rows) return v;
-    const float* p = X + row * K + k;
-    if (vec) {
-        if (k + 4 <= K) v = *reinterpret_cast<const f32x4*>(p);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (k + r < K) v[r] = p[r];
-    }
-    return v;
-}
-
 __device__ __forceinline__ float relu(float t) { return t < 0.f ? 0.f : t; }   // a NaN stays one
 
 __device__ __forceinline__ f32x4 load_act(const Act& a, int64_t row, int k) {
@@ -119,15 +108,6 @@ __device__ __forceinline__ f32x4 load_act(const Act& a, int64_t row, int k) {
         if (a.pro == PRO_BN) t = (t - a.mean[k + r]) * a.scale[k + r] + a.beta[k + r];
         v[r] = relu(t);
     }
-    return v;
-}
-
-template <typename T>
-__device__ __forceinline__ T sum16(T v) {      // over the 16 lanes that share g: every lane gets the sum
-    v += __shfl_xor(v, 1);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 4);
-    v += __shfl_xor(v, 8);
     return v;
 }
 
@@ -149,6 +129,18 @@ __device__ __forceinline__ void col_reduce(float (&v)[2], float* red, int wave, 
     for (int tn = 0; tn < 2; ++tn) {
         const int e = 16 * tn + c;
         v[tn] = ((red[e] + red[AE_BN + e]) + red[2 * AE_BN + e]) + red[3 * AE_BN + e];
+    }
+}
+
+// The layer kernels' sum over k in two levels: part, the fmaf chain of the MFMAs, ends after AE_CHAIN k blocks
+// and at the last one, and the chains are added in order onto tot (which starts as the bias, or zero).
+__device__ __forceinline__ void chain_fold(int k0, int K, f32x4 (&part)[2], f32x4 (&tot)[2]) {
+    if ((k0 / AE_BK) % AE_CHAIN == AE_CHAIN - 1 || k0 + AE_BK >= K) {
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn) {
+            tot[tn] += part[tn];
+            part[tn] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
     }
 }
 
@@ -177,55 +169,22 @@ __global__ void __launch_bounds__(AE_THREADS) k_ae_fwd(const FwdArgs a) {
     const int n0 = blockIdx.x * AE_BN, K = a.in.width, N = a.N;
     const bool vw = a.vec_w != 0;
 
-    // the sum over k in two levels: chains of AE_CHAIN k blocks, added in order onto the bias
-    f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}}, tot[2];
+    f32x4 part[1][2] = {{f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}}}, tot[2];
 #pragma unroll
     for (int tn = 0; tn < 2; ++tn) {
         const int col = n0 + 16 * tn + c;
         const float b = col < N ? a.bias[col] : 0.f;
         tot[tn] = f32x4{b, b, b, b};
     }
-
-    // thread t stages float4 t and t + 256 of the 64 x 32 activation tile and float4 t of the 32 x 32 weight tile
-    const int s_row = tid >> 3, s_k = (tid & 7) * 4;
-    f32x4 ra[2], rw;
-    ra[0] = load_act(a.in, m0 + s_row, s_k);
-    ra[1] = load_act(a.in, m0 + s_row + 32, s_k);
-    rw = load4(a.W, n0 + s_row, N, s_k, K, vw);
-    for (int k0 = 0; k0 < K; k0 += AE_BK) {
-        __syncthreads();                                   // the previous block's reads are done
-        *reinterpret_cast<f32x4*>(As + s_row * AE_LDK + s_k) = ra[0];
-        *reinterpret_cast<f32x4*>(As + (s_row + 32) * AE_LDK + s_k) = ra[1];
-        *reinterpret_cast<f32x4*>(Ws + s_row * AE_LDK + s_k) = rw;
-        __syncthreads();
-        if (k0 + AE_BK < K) {
-            ra[0] = load_act(a.in, m0 + s_row, k0 + AE_BK + s_k);
-            ra[1] = load_act(a.in, m0 + s_row + 32, k0 + AE_BK + s_k);
-            rw = load4(a.W, n0 + s_row, N, k0 + AE_BK + s_k, K, vw);
-        }
-#pragma unroll
-        for (int s = 0; s < AE_BK / 16; ++s) {
-            if (k0 + 16 * s >= K) break;                   // a K tail of at most 16: the second half is all zero
-            const f32x4 fa = *reinterpret_cast<const f32x4*>(As + (16 * wave + c) * AE_LDK + 16 * s + 4 * g);
-            f32x4 fb[2];
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn)
-                fb[tn] = *reinterpret_cast<const f32x4*>(Ws + (16 * tn + c) * AE_LDK + 16 * s + 4 * g);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int tn = 0; tn < 2; ++tn) acc[tn] = mfma4(fa[r], fb[tn][r], acc[tn]);
-        }
-        if ((k0 / AE_BK) % AE_CHAIN == AE_CHAIN - 1 || k0 + AE_BK >= K) {
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn) {
-                tot[tn] += acc[tn];
-                acc[tn] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-        }
-    }
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn) acc[tn] = tot[tn];
+    // the 64 x 32 activation tile (2 float4 per thread) and the 32 x 32 weight tile (1)
+    lsr::dense_k_loop<2, 1>(
+        K, As, Ws, [=](int row, int k0, int k) { return load_act(a.in, m0 + row, k0 + k); },
+        [=](int row, int k0, int k) { return load4(a.W, n0 + row, N, k0 + k, K, vw); },
+        [&](int k0) {
+            lsr::dense_tile_mma(As, Ws, 16 * wave, 0, k0, K, part);
+            chain_fold(k0, K, part[0], tot);
+        });
+    const f32x4(&acc)[2] = tot;
 
     // lane (c, g), register r of tile tn: row m0 + 16 wave + 4 g + r, column n0 + 16 tn + c
     const int64_t row0 = m0 + 16 * wave + 4 * g;
@@ -422,43 +381,25 @@ __global__ void __launch_bounds__(AE_THREADS) k_ae_dx(const DxArgs a) {
     const int k0 = blockIdx.x * AE_BN, B = a.B, N = a.N, K = a.K;
     const bool vg = a.vec_g != 0, vw = a.vec_w != 0;
 
-    f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}}, tot[2] = {acc[0], acc[0]};   // as k_ae_fwd
-    const int s_row = tid >> 3, s_k = (tid & 7) * 4;
-    f32x4 rg[2], rw;
-    rg[0] = load4(a.dH, s_row, B, s_k, N, vg);
-    rg[1] = load4(a.dH, s_row + 32, B, s_k, N, vg);
-    rw = load4(a.W, s_row, N, k0 + s_k, K, vw);
-    for (int n0 = 0; n0 < N; n0 += AE_BK) {
-        __syncthreads();
-        *reinterpret_cast<f32x4*>(Gs + s_row * AE_LDK + s_k) = rg[0];
-        *reinterpret_cast<f32x4*>(Gs + (s_row + 32) * AE_LDK + s_k) = rg[1];
-        *reinterpret_cast<f32x4*>(Ws + s_row * AE_LDK + s_k) = rw;
-        __syncthreads();
-        if (n0 + AE_BK < N) {
-            rg[0] = load4(a.dH, s_row, B, n0 + AE_BK + s_k, N, vg);
-            rg[1] = load4(a.dH, s_row + 32, B, n0 + AE_BK + s_k, N, vg);
-            rw = load4(a.W, n0 + AE_BK + s_row, N, k0 + s_k, K, vw);
-        }
+    f32x4 part[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}}, tot[2] = {part[0], part[0]};
+    // the reduction runs over n: the 64 x 32 tile of dH, and W's rows n0 .. n0 + 31 at the slab's columns
+    lsr::dense_k_loop<2, 1>(
+        N, Gs, Ws, [=](int row, int n0, int n) { return load4(a.dH, row, B, n0 + n, N, vg); },
+        [=](int row, int n0, int k) { return load4(a.W, n0 + row, N, k0 + k, K, vw); },
+        [&](int n0) {
 #pragma unroll
-        for (int s = 0; s < AE_BK / 16; ++s) {
-            if (n0 + 16 * s >= N) break;
-            const f32x4 fa = *reinterpret_cast<const f32x4*>(Gs + (16 * wave + c) * AE_LDK + 16 * s + 4 * g);
+            for (int s = 0; s < AE_BK / 16; ++s) {
+                if (n0 + 16 * s >= N) break;               // a tail of at most 16: the second half is all zero
+                const f32x4 fa = *reinterpret_cast<const f32x4*>(Gs + (16 * wave + c) * AE_LDK + 16 * s + 4 * g);
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
+                for (int r = 0; r < 4; ++r)
 #pragma unroll
-                for (int tn = 0; tn < 2; ++tn)
-                    acc[tn] = mfma4(fa[r], Ws[(16 * s + 4 * g + r) * AE_LDK + 16 * tn + c], acc[tn]);
-        }
-        if ((n0 / AE_BK) % AE_CHAIN == AE_CHAIN - 1 || n0 + AE_BK >= N) {
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn) {
-                tot[tn] += acc[tn];
-                acc[tn] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    for (int tn = 0; tn < 2; ++tn)         // B[k = n][col]: W's tile read down its rows
+                        part[tn] = mfma4(fa[r], Ws[(16 * s + 4 * g + r) * AE_LDK + 16 * tn + c], part[tn]);
             }
-        }
-    }
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn) acc[tn] = tot[tn];
+            chain_fold(n0, N, part, tot);
+        });
+    const f32x4(&acc)[2] = tot;
 
     // lane (c, g), register r of tile tn: row 16 wave + 4 g + r, column k0 + 16 tn + c of dA
     const int row0 = 16 * wave + 4 * g;
@@ -753,25 +694,21 @@ EvalWs eval_layout(const lsr_autoencoder& n, int64_t n_rows, void* base) {
 
 int check_ws(const std::string& w, const void* ws, int64_t ws_bytes, size_t need) {
     if (!ws) return lsr::fail(LSR_EINVAL, w + ": the workspace is required");
-    if (!aligned16(ws)) return lsr::fail(LSR_EINVAL, w + ": the workspace must be 16-byte aligned");
-    if (ws_bytes < (int64_t)need)
-        return lsr::fail(LSR_EINVAL, w + ": the workspace holds " + std::to_string(ws_bytes) + " bytes, " + std::to_string(need) +
-                                         " are needed (lsr_ae_workspace_size)");
-    return LSR_OK;
+    return lsr::check_ws(w + ": ", ws, ws_bytes, (int64_t)need, "lsr_ae_workspace_size");
 }
 
 Act act_of(const float* X, int64_t rows, int width, int pro = PRO_NONE, const float* scale = nullptr,
            const float* mean = nullptr, const float* beta = nullptr) {
     Act a{};
     a.X = X; a.scale = scale; a.mean = mean; a.beta = beta; a.rows = rows; a.width = width; a.pro = pro;
-    a.vec = width % 4 == 0 && aligned16(X);
+    a.vec = rows_vec(X, width);
     return a;
 }
 
 template <int EPI>
 void launch_fwd(FwdArgs& a, const float* W, const float* bias, int N, hipStream_t st) {
     a.W = W; a.bias = bias; a.N = N;
-    a.vec_w = a.in.width % 4 == 0 && aligned16(W);
+    a.vec_w = rows_vec(W, a.in.width);
     const dim3 grid((unsigned)((N + AE_BN - 1) / AE_BN), (unsigned)((a.in.rows + AE_BM - 1) / AE_BM));
     hipLaunchKernelGGL(k_ae_fwd<EPI>, grid, dim3(AE_THREADS), 0, st, a);
 }
@@ -939,7 +876,7 @@ extern "C" int lsr_ae_train_step(const lsr_autoencoder* net, const lsr_ae_params
 
     auto launch_dw = [&](const float* dH, const Act& in, int N, Moments wt, Moments bs) {
         DwArgs a{};
-        a.dH = dH; a.in = in; a.N = N; a.vec_g = N % 4 == 0 && aligned16(dH);
+        a.dH = dH; a.in = in; a.N = N; a.vec_g = rows_vec(dH, N);
         a.w = wt; a.b = bs; a.h = h;
         const dim3 grid((unsigned)((in.width + AE_BN - 1) / AE_BN), (unsigned)((N + AE_DW_BN - 1) / AE_DW_BN));
         hipLaunchKernelGGL(k_ae_dw_adam, grid, dim3(AE_THREADS), 0, st, a);
@@ -947,8 +884,8 @@ extern "C" int lsr_ae_train_step(const lsr_autoencoder* net, const lsr_ae_params
     auto dx_args = [&](const float* dH, const float* W, int N, int K, const float* Hprev, float* dHprev) {
         DxArgs a{};
         a.dH = dH; a.W = W; a.Hprev = Hprev; a.dHprev = dHprev; a.B = B; a.N = N; a.K = K;
-        a.vec_g = N % 4 == 0 && aligned16(dH);
-        a.vec_w = K % 4 == 0 && aligned16(W);
+        a.vec_g = rows_vec(dH, N);
+        a.vec_w = rows_vec(W, K);
         a.h = h;
         return a;
     };

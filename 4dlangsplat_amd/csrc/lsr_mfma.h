@@ -1,5 +1,5 @@
 // lsr_mfma.h -- matrix-core helpers: the bf16 MFMA of the compositor backward (render_bwd_wave.hip) and the
-// f32-input MFMA of the query and PCA kernels.
+// f32-input MFMA of the query, PCA, video-decoder and autoencoder kernels (the last two through lsr_dense.h).
 //
 // v_mfma_f32_16x16x32_bf16 lane maps (checked bit-exactly by tests/kernels/t_mfma16.hip):
 //   A (16 x 32): lane l holds A[l & 15][8 (l >> 4) + j], j = 0..7
@@ -18,7 +18,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define LSR_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
-// v_mfma_f32_16x16x4_f32, the exact f32-input MFMA (query.hip, pca.hip): lane l = (c = l & 15, g = l >> 4)
+// v_mfma_f32_16x16x4_f32, the exact f32-input MFMA (query.hip, pca.hip, lsr_dense.h): lane l = (c = l & 15, g = l >> 4)
 // holds A[row c][k = g], B[k = g][col c] and D[row 4 g + reg][col c].
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);

@@ -31,6 +31,7 @@
 
 #include "../../include/lsr.h"
 #include "../../include/lsr_query.h"
+#include "lsr_dense.h"
 #include "lsr_host.h"
 #include "lsr_mfma.h"
 #include "lsr_wave.h"
@@ -38,9 +39,9 @@
 namespace {
 
 using lsr::aligned16;
+using lsr::f32x4;
 using lsr::lds_float;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kWaves = 8;
@@ -342,19 +343,7 @@ lsr::ApiGate g_query_api{"lsr_query", "LSR_QUERY_API_VERSION", LSR_QUERY_API_VER
 
 int check_decoder(const lsr_decoder* d) {
     if (int rc = g_query_api.check()) return rc;
-    if (!d) return lsr::fail(LSR_EINVAL, "null decoder");
-    if (d->n_layers < 1 || d->n_layers > LSR_QUERY_MAX_LAYERS)
-        return lsr::fail(LSR_EINVAL, "n_layers must be in [1, " + std::to_string(LSR_QUERY_MAX_LAYERS) + "]");
-    if (d->dims[0] < 1 || d->dims[0] > LSR_QUERY_MAX_INPUT)
-        return lsr::fail(LSR_EINVAL, "c_in = dims[0] must be in [1, " + std::to_string(LSR_QUERY_MAX_INPUT) + "]");
-    for (int i = 1; i <= d->n_layers; ++i)
-        if (d->dims[i] < 16 || d->dims[i] > LSR_QUERY_MAX_WIDTH || d->dims[i] % 16)
-            return lsr::fail(LSR_EINVAL, "layer width " + std::to_string(d->dims[i]) + ": every width after c_in must "
-                                         "be a multiple of 16 and at most " + std::to_string(LSR_QUERY_MAX_WIDTH));
-    for (int i = 0; i < d->n_layers; ++i)
-        if (!d->weight[i] || !d->bias[i])
-            return lsr::fail(LSR_EINVAL, "missing weight or bias of decoder layer " + std::to_string(i));
-    return LSR_OK;
+    return lsr::check_decoder("", d, LSR_QUERY_MAX_WIDTH, true);
 }
 
 template <bool RELEVANCY>

@@ -5,7 +5,8 @@
 // k_video_layer<LAST>  C = A . W^T + b for one layer: A [M, K] the (already ReLU'd) activations, W [N, K]
 //                      nn.Linear's weight.  A block of 4 waves owns VQ_BM = 128 rows x VQ_BN = 128 output
 //                      features, wave (wm, wn) a 64 x 64 quarter of it as 4 x 4 MFMA tiles (64 accumulator
-//                      registers).  K runs in blocks of VQ_BK = 32: both operands' 128 x 32 tiles go
+//                      registers).  K runs in blocks of VQ_BK = 32 (lsr_dense.h's dense_k_loop and
+//                      dense_tile_mma, shared with the autoencoder): both operands' 128 x 32 tiles go
 //                      global -> registers -> LDS (rows padded to 36 floats), the next block's loads in flight
 //                      while this one is multiplied, so each weight byte fetched meets 128 rows (64 FLOP) and
 //                      each activation byte 128 features.  Rows past M, features past N and k past K are
@@ -32,19 +33,20 @@
 
 #include "../../include/lsr.h"
 #include "../../include/lsr_video.h"
+#include "lsr_dense.h"
 #include "lsr_host.h"
 #include "lsr_mfma.h"
 #include "lsr_wave.h"
 
 namespace {
 
-using lsr::aligned16;
 using lsr::f32x4;
-using lsr::mfma4;
+using lsr::load4;
+using lsr::sum16;
 
-constexpr int VQ_BM = LSR_VIDEO_ROW_TILE, VQ_BN = LSR_VIDEO_COL_TILE, VQ_BK = 32;
-constexpr int VQ_LDK = VQ_BK + 4;                 // LDS row stride in floats (16-byte aligned rows)
-constexpr int VQ_THREADS = 256;
+constexpr int VQ_BM = LSR_VIDEO_ROW_TILE, VQ_BN = LSR_VIDEO_COL_TILE, VQ_BK = lsr::DENSE_BK;
+constexpr int VQ_LDK = lsr::DENSE_LDK;            // LDS row stride in floats (16-byte aligned rows)
+constexpr int VQ_THREADS = lsr::DENSE_THREADS;
 constexpr int VQ_NV = 1 + LSR_VIDEO_MAX_QUERIES;  // values of one row's partial sum: ssq, then the dots
 constexpr int VQ_LOADS = VQ_BM * VQ_BK / 4 / VQ_THREADS;   // float4 of one operand tile per thread: 4
 static_assert(VQ_BM == 128 && VQ_BN == 128, "the wave layout is 2 x 2 quarters of 64 x 64");
@@ -61,29 +63,6 @@ struct LayerArgs {
     int32_t K, N, n_q;
     int32_t vec_a, vec_w;   // rows of A / W can be fetched 16 bytes at a time
 };
-
-// X[row][k .. k + 3] of a [rows, K] matrix, zero outside it
-__device__ __forceinline__ f32x4 load4(const float* __restrict__ X, int64_t row, int64_t n_rows, int k, int K, bool vec) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (row >= n_rows) return v;
-    const float* p = X + row * K + k;
-    if (vec) {
-        if (k + 4 <= K) v = *reinterpret_cast<const f32x4*>(p);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (k + r < K) v[r] = p[r];
-    }
-    return v;
-}
-
-__device__ __forceinline__ float sum16(float v) {      // over the 16 lanes that share g: every lane gets the sum
-    v += __shfl_xor(v, 1);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 4);
-    v += __shfl_xor(v, 8);
-    return v;
-}
 
 template <bool LAST>
 __global__ void __launch_bounds__(VQ_THREADS) k_video_layer(const LayerArgs a) {
@@ -108,48 +87,12 @@ __global__ void __launch_bounds__(VQ_THREADS) k_video_layer(const LayerArgs a) {
         for (int tm = 0; tm < 4; ++tm) acc[tm][tn] = f32x4{b, b, b, b};
     }
 
-    // thread t stages float4 number t + 256 i of each tile: row (t + 256 i) / 8, k offset 4 ((t + 256 i) % 8)
-    f32x4 ra[VQ_LOADS], rw[VQ_LOADS];
-    const int s_row = tid >> 3, s_k = (tid & 7) * 4;
-#pragma unroll
-    for (int i = 0; i < VQ_LOADS; ++i) {
-        ra[i] = load4(a.A, m0 + s_row + 32 * i, a.M, s_k, K, va);
-        rw[i] = load4(a.W, n0 + s_row + 32 * i, N, s_k, K, vw);
-    }
-    for (int k0 = 0; k0 < K; k0 += VQ_BK) {
-        __syncthreads();                                   // the previous block's reads are done
-#pragma unroll
-        for (int i = 0; i < VQ_LOADS; ++i) {
-            *reinterpret_cast<f32x4*>(As + (s_row + 32 * i) * VQ_LDK + s_k) = ra[i];
-            *reinterpret_cast<f32x4*>(Ws + (s_row + 32 * i) * VQ_LDK + s_k) = rw[i];
-        }
-        __syncthreads();
-        if (k0 + VQ_BK < K) {
-#pragma unroll
-            for (int i = 0; i < VQ_LOADS; ++i) {
-                ra[i] = load4(a.A, m0 + s_row + 32 * i, a.M, k0 + VQ_BK + s_k, K, va);
-                rw[i] = load4(a.W, n0 + s_row + 32 * i, N, k0 + VQ_BK + s_k, K, vw);
-            }
-        }
-        if (active) {
-#pragma unroll
-            for (int s = 0; s < VQ_BK / 16; ++s) {
-                if (k0 + 16 * s >= K) break;               // a K tail of at most 16: the second half is all zero
-                f32x4 fa[4], fb[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    fa[t] = *reinterpret_cast<const f32x4*>(As + (64 * wm + 16 * t + c) * VQ_LDK + 16 * s + 4 * g);
-                    fb[t] = *reinterpret_cast<const f32x4*>(Ws + (64 * wn + 16 * t + c) * VQ_LDK + 16 * s + 4 * g);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                        for (int tn = 0; tn < 4; ++tn) acc[tm][tn] = mfma4(fa[tm][r], fb[tn][r], acc[tm][tn]);
-            }
-        }
-    }
+    lsr::dense_k_loop<VQ_LOADS, VQ_LOADS>(
+        K, As, Ws, [=](int row, int k0, int k) { return load4(a.A, m0 + row, a.M, k0 + k, K, va); },
+        [=](int row, int k0, int k) { return load4(a.W, n0 + row, N, k0 + k, K, vw); },
+        [&](int k0) {
+            if (active) lsr::dense_tile_mma(As, Ws, 64 * wm, 64 * wn, k0, K, acc);   // one fmaf chain, on the bias
+        });
 
     if constexpr (!LAST) {
         if (!active) return;
@@ -242,15 +185,7 @@ int check_api(const char* what) { return g_video_api.check(what); }
 int check_shapes(const char* what, const lsr_decoder* d, int64_t n_rows) {
     const std::string w(what);
     if (int rc = check_api(what)) return rc;
-    if (!d) return lsr::fail(LSR_EINVAL, w + ": null decoder");
-    if (d->n_layers < 1 || d->n_layers > LSR_QUERY_MAX_LAYERS)
-        return lsr::fail(LSR_EINVAL, w + ": n_layers must be in [1, " + std::to_string(LSR_QUERY_MAX_LAYERS) + "]");
-    if (d->dims[0] < 1 || d->dims[0] > LSR_QUERY_MAX_INPUT)
-        return lsr::fail(LSR_EINVAL, w + ": c_in = dims[0] must be in [1, " + std::to_string(LSR_QUERY_MAX_INPUT) + "]");
-    for (int i = 1; i <= d->n_layers; ++i)
-        if (d->dims[i] < 16 || d->dims[i] > LSR_VIDEO_MAX_WIDTH || d->dims[i] % 16)
-            return lsr::fail(LSR_EINVAL, w + ": layer width " + std::to_string(d->dims[i]) + ": every width after c_in "
-                                         "must be a multiple of 16 and at most " + std::to_string(LSR_VIDEO_MAX_WIDTH));
+    if (int rc = lsr::check_decoder(w + ": ", d, LSR_VIDEO_MAX_WIDTH, false)) return rc;
     if (n_rows < 0) return lsr::fail(LSR_EINVAL, w + ": n_rows must be >= 0");
     if ((n_rows + VQ_BM - 1) / VQ_BM > 0x7fffffffLL) return lsr::fail(LSR_EINVAL, w + ": n_rows too large for one launch");
     return LSR_OK;
@@ -287,20 +222,16 @@ extern "C" int64_t lsr_video_workspace_bytes(const lsr_decoder* dec, int64_t n_r
 extern "C" int lsr_video_cosine(const lsr_decoder* dec, int64_t n_rows, const float* rows, int32_t n_q,
                                 const float* queries, float* cosine, void* ws, int64_t ws_bytes, void* stream) {
     if (int rc = check_shapes("lsr_video_cosine", dec, n_rows)) return rc;
+    // the layers' tensors: refused after n_rows, so the dims pass once more
+    if (int rc = lsr::check_decoder("lsr_video_cosine: ", dec, LSR_VIDEO_MAX_WIDTH, true)) return rc;
     const lsr_decoder& d = *dec;
-    for (int i = 0; i < d.n_layers; ++i)
-        if (!d.weight[i] || !d.bias[i])
-            return lsr::fail(LSR_EINVAL, "lsr_video_cosine: missing weight or bias of decoder layer " + std::to_string(i));
     if (n_q < 1 || n_q > LSR_VIDEO_MAX_QUERIES)
         return lsr::fail(LSR_EINVAL, "lsr_video_cosine: n_q must be in [1, " + std::to_string(LSR_VIDEO_MAX_QUERIES) +
                                          "], got " + std::to_string(n_q));
     if (!rows || !queries || !cosine || !ws)
         return lsr::fail(LSR_EINVAL, "lsr_video_cosine: rows, queries, cosine and the workspace are required");
-    if (!aligned16(ws)) return lsr::fail(LSR_EINVAL, "lsr_video_cosine: the workspace must be 16-byte aligned");
     const Layout l = layout_of(d, n_rows);
-    if (ws_bytes < l.total)
-        return lsr::fail(LSR_EINVAL, "lsr_video_cosine: the workspace holds " + std::to_string(ws_bytes) + " bytes, " +
-                                         std::to_string(l.total) + " are needed (lsr_video_workspace_bytes)");
+    if (int rc = lsr::check_ws("lsr_video_cosine: ", ws, ws_bytes, l.total, "lsr_video_workspace_bytes")) return rc;
     if (n_rows == 0) return LSR_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char* base = static_cast<char*>(ws);
@@ -313,8 +244,8 @@ extern "C" int lsr_video_cosine(const lsr_decoder* dec, int64_t n_rows, const fl
         LayerArgs a{};
         a.A = in; a.W = d.weight[i]; a.bias = d.bias[i];
         a.M = n_rows; a.K = d.dims[i]; a.N = d.dims[i + 1];
-        a.vec_a = a.K % 4 == 0 && aligned16(a.A);
-        a.vec_w = a.K % 4 == 0 && aligned16(a.W);
+        a.vec_a = lsr::rows_vec(a.A, a.K);
+        a.vec_w = lsr::rows_vec(a.W, a.K);
         const dim3 grid(row_tiles, (unsigned)((a.N + VQ_BN - 1) / VQ_BN));
         if (last) {
             a.q = queries; a.n_q = n_q; a.partial = partial;

@@ -48,6 +48,18 @@ def test_radix_sort(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
 
 
+def test_dense_blocks(tmp_path):
+    """The dense-layer units' staged k loop and tile multiply (lsr_dense.h) in the library's instantiations,
+    exact against host integer sums around every tail, block count, row-tile edge and fetch path."""
+    src = os.path.join(ROOT, "tests", "kernels", "t_dense_blocks.hip")
+    exe = str(tmp_path / "t_dense")
+    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
+                    "-I", os.path.join(ROOT, "4dlangsplat_amd", "csrc"), "-o", exe, src], check=True)
+    r = subprocess.run(["timeout", "-k", "5", "60", exe], capture_output=True, text=True)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
 def test_lds_dma_row_gather(tmp_path):
     """LDS-DMA (global_load_lds, 16 B per lane) row gather as the forward compositor's staged
     variant uses it: lane-linear LDS image, per-lane source rows."""
