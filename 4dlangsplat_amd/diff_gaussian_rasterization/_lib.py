@@ -153,6 +153,13 @@ AE_MAX_WIDTH = 4096         # LSR_AE_MAX_WIDTH
 AE_MAX_LATENT = 32          # LSR_AE_MAX_LATENT
 AE_MAX_BATCH = 64           # LSR_AE_MAX_BATCH
 AE_EVAL_CHUNK = 2048        # LSR_AE_EVAL_CHUNK
+TILES_LEVELS = 4            # LSR_TILES_LEVELS (include/lsr_tiles.h)
+TILES_MAX_LABEL = 1023      # LSR_TILES_MAX_LABEL
+TILES_MAX_TILES = 4 * 1023  # LSR_TILES_MAX_TILES
+TILES_SIDE = 224            # LSR_TILES_SIDE
+TILES_MAX_SIDE = 16384      # LSR_TILES_MAX_SIDE
+TILES_DESC_INTS = 6         # LSR_TILES_DESC_INTS
+TILES_COUNTS = 5            # LSR_TILES_COUNTS
 
 _vp = ctypes.c_void_p
 SIGNATURES = {
@@ -324,6 +331,12 @@ SIGNATURES = {
     "lsr_ae_train_step": (ctypes.c_int, [ctypes.POINTER(Autoencoder), ctypes.POINTER(AeParams),
                                          ctypes.POINTER(AeParams), ctypes.c_int32, _vp] + [ctypes.c_double] * 4
                           + [ctypes.c_int64, ctypes.c_double, _vp, _vp, ctypes.c_int64, _vp]),
+    "lsr_tiles_workspace_size": (ctypes.c_int64, [ctypes.c_int32]),
+    "lsr_tiles_census": (ctypes.c_int, [ctypes.c_int32] * 3 + [_vp, ctypes.c_int64, _vp, _vp]),
+    "lsr_tiles_plan": (ctypes.c_int, [ctypes.c_int32] * 3 + [ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    "lsr_tiles_render": (ctypes.c_int, [ctypes.c_int32] * 3 + [_vp, _vp, ctypes.c_int64, _vp, _vp,
+                                                               ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, _vp, _vp,
+                                                               _vp]),
     "lsr_profile_read": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
                                         ctypes.c_int32]),
 }
