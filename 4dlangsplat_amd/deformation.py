@@ -85,6 +85,7 @@ class DeformationField:
             raise ValueError(f"deformation parameters do not match the configuration: unexpected {extra}, "
                              f"missing {missing}")
         self.p = {k: v.detach().to(self.device, torch.float32).contiguous() for k, v in params.items()}
+        self._B = _lib.Boundary(self.p["grid.aabb"].device)   # the parameters' device, with its index
         # the network shape is the parameters' own: feature_out.0.weight is [width, channels S], a plane
         # [1, channels, H, W]
         self.width = int(self.p["feature_out.0.weight"].shape[0])
@@ -158,22 +159,27 @@ class DeformationField:
         n.heads = sum(1 << h for h, on in enumerate(self.head_on) if on) | (32 if coff_head else 0)
         n.apply_rotation = int(self.apply_rotation)
         n.lang_mode, n.lang_dim, n.centers, n.time_pe = lang_mode, self.lang_dim, self.centers, self.time_pe
-        n.aabb = self.p["grid.aabb"].data_ptr()
+        self._fill(n, self.p)
+        n.aabb = self._B.ptr(self.p["grid.aabb"], "grid.aabb")
+        return n
+
+    def _fill(self, c, tensors):
+        """The plane and weight pointers of a DeformNet (tensors: the parameters) or DeformGrads (their gradients)"""
+        def ptr(k):
+            return self._B.ptr(tensors[k], k)
+
         for s in range(len(self.multires)):
             for ci in range(6):
-                n.planes[s][ci] = self.p[f"grid.grids.{s}.{ci}"].data_ptr()
+                c.planes[s][ci] = ptr(f"grid.grids.{s}.{ci}")
         for k in range(self.n_layers):
-            n.w_feat[k], n.b_feat[k] = self.p[f"feature_out.{2 * k}.weight"].data_ptr(), \
-                self.p[f"feature_out.{2 * k}.bias"].data_ptr()
+            c.w_feat[k], c.b_feat[k] = ptr(f"feature_out.{2 * k}.weight"), ptr(f"feature_out.{2 * k}.bias")
         for h, name in enumerate(HEADS + (COFF,)):
             if name in self.heads_computed():
-                n.w1[h], n.b1[h] = self.p[name + ".1.weight"].data_ptr(), self.p[name + ".1.bias"].data_ptr()
-                n.w2[h], n.b2[h] = self.p[name + ".3.weight"].data_ptr(), self.p[name + ".3.bias"].data_ptr()
+                c.w1[h], c.b1[h] = ptr(name + ".1.weight"), ptr(name + ".1.bias")
+                c.w2[h], c.b2[h] = ptr(name + ".3.weight"), ptr(name + ".3.bias")
         if self.lang_mode in (LANG_RESIDUAL, LANG_NORESNET):
             for i, k in enumerate((1, 3, 5)):
-                n.w_lang[i], n.b_lang[i] = self.p[f"lang_deform.{k}.weight"].data_ptr(), \
-                    self.p[f"lang_deform.{k}.bias"].data_ptr()
-        return n
+                c.w_lang[i], c.b_lang[i] = ptr(f"lang_deform.{k}.weight"), ptr(f"lang_deform.{k}.bias")
 
     def _call_net(self, no_dlang: Optional[bool]):
         """The net of one call: the reference's render() forces no_dlang = 1 in the 'base' stages
@@ -335,9 +341,8 @@ class DeformationField:
     def prepare(self):
         """Repack planes and weights (call after every parameter update)."""
         L = _lib.load()
-        _lib.check(L.lsr_deform_prepare(ctypes.byref(self.net), ctypes.c_void_p(self.workspace.data_ptr()),
-                                        ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
-                   "lsr_deform_prepare")
+        _lib.check(L.lsr_deform_prepare(ctypes.byref(self.net), self._B.ptr(self.workspace, "workspace", torch.uint8),
+                                        self._B.stream()), "lsr_deform_prepare")
 
     # ---- forward -----------------------------------------------------------------------------------
     def _time(self, time, P):
@@ -365,11 +370,11 @@ class DeformationField:
         out_coff = torch.empty(P, self.centers, device=self.device) if net.lang_mode == LANG_DISCRETE else None
         if net.lang_mode != LANG_PASS and lang_in is None:
             raise ValueError("this field deforms the language feature: lang is required")
-        vp = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None else 0)   # noqa: E731
-        _lib.check(L.lsr_deform_forward(ctypes.byref(net), vp(self.workspace), P, *[vp(x) for x in ins], vp(lang_in),
-                                        vp(t), *[vp(x) for x in outs], vp(out_lang), vp(out_coff),
-                                        ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
-                   "lsr_deform_forward")
+        B = self._B
+        _lib.check(L.lsr_deform_forward(ctypes.byref(net), B.ptr(self.workspace, "workspace", torch.uint8), P,
+                                        *[B.ptr(x, "input") for x in ins], B.opt(lang_in, "lang"), B.ptr(t, "time"),
+                                        *[B.opt(x, "output") for x in outs], B.opt(out_lang, "lang output"),
+                                        B.opt(out_coff, "coff output"), B.stream()), "lsr_deform_forward")
         res = [o if o is not None else x for o, x in zip(outs, ins)]
         if net.lang_mode == LANG_PASS:
             out_lang = lang[:, :self.lang_dim] if lang is not None else None
@@ -446,33 +451,21 @@ class DeformationField:
         dm = torch.empty_like(m)
         drot = torch.empty(P, 4, device=self.device) if self.apply_rotation else None
         dlang = torch.empty(P, self.lang_in, device=self.device) if net.lang_mode != LANG_PASS else None
-        g = _lib.DeformGrads()
-        for s in range(len(self.multires)):
-            for ci in range(6):
-                g.planes[s][ci] = self.grads[f"grid.grids.{s}.{ci}"].data_ptr()
-        for k in range(self.n_layers):
-            g.w_feat[k] = self.grads[f"feature_out.{2 * k}.weight"].data_ptr()
-            g.b_feat[k] = self.grads[f"feature_out.{2 * k}.bias"].data_ptr()
-        for h, name in enumerate(HEADS + (COFF,)):
-            if name in self.heads_computed():
-                g.w1[h], g.b1[h] = self.grads[name + ".1.weight"].data_ptr(), self.grads[name + ".1.bias"].data_ptr()
-                g.w2[h], g.b2[h] = self.grads[name + ".3.weight"].data_ptr(), self.grads[name + ".3.bias"].data_ptr()
-        if self.lang_mode in (LANG_RESIDUAL, LANG_NORESNET):
-            for i, k in enumerate((1, 3, 5)):
-                g.w_lang[i] = self.grads[f"lang_deform.{k}.weight"].data_ptr()
-                g.b_lang[i] = self.grads[f"lang_deform.{k}.bias"].data_ptr()
-        if "grid.aabb" in self.grads:
-            g.aabb = self.grads["grid.aabb"].data_ptr()
+        g, B = _lib.DeformGrads(), self._B
+        self._fill(g, self.grads)
+        g.aabb = B.opt(self.grads.get("grid.aabb"), "grid.aabb gradient")
         nbytes = int(L.lsr_deform_backward_scratch_bytes(ctypes.byref(net), P))
         if nbytes < 0:
             _lib.check(1, "lsr_deform_backward_scratch_bytes")
         if getattr(self, "_scratch", None) is None or self._scratch.numel() < nbytes:
             self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        vp = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None else 0)   # noqa: E731
-        _lib.check(L.lsr_deform_backward(ctypes.byref(net), vp(self.workspace), P, vp(m), vp(rot), vp(lang_in), vp(t),
-                                         *[vp(u) for u in ups], vp(dl_up), vp(f(d_coff, (P, self.centers)) if net.lang_mode == LANG_DISCRETE else None), vp(dm),
-                                         vp(drot), vp(dlang), ctypes.byref(g), vp(self._scratch),
-                                         ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+        dc_up = f(d_coff, (P, self.centers)) if net.lang_mode == LANG_DISCRETE else None
+        _lib.check(L.lsr_deform_backward(ctypes.byref(net), B.ptr(self.workspace, "workspace", torch.uint8), P,
+                                         B.ptr(m, "means3D"), B.opt(rot, "rotations"), B.opt(lang_in, "lang"),
+                                         B.ptr(t, "time"), *[B.opt(u, "output gradient") for u in ups],
+                                         B.opt(dl_up, "d_lang"), B.opt(dc_up, "d_coff"), B.ptr(dm, "d_means3D"),
+                                         B.opt(drot, "d_rotations"), B.opt(dlang, "d_lang input"), ctypes.byref(g),
+                                         B.ptr(self._scratch, "scratch", torch.uint8), B.stream()),
                    "lsr_deform_backward")
         # identity residuals (and heads that are off) pass their output gradient to the input
         d_in = [dm, ups[1] if ups[1] is not None else f(d_scales, (P, 3)),

@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import ctypes
 import functools
-from typing import NamedTuple, Optional
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -54,10 +54,6 @@ class GaussianRasterizationSettings(NamedTuple):
     include_feature: bool = True
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def _opt(t):
     """upstream passes torch.Tensor([]) for 'not provided'"""
     if t is None or t.numel() == 0:
@@ -78,10 +74,6 @@ def _settings_array(settings):
     return _struct_array(_lib.Settings, [s.c for s in settings])     # of _NativeSettings
 
 
-def _ptr_array(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
 def _int64_array(values):
     return (ctypes.c_int64 * len(values))(*values)
 
@@ -96,12 +88,13 @@ class _NativeSettings:
         self.campos = _f32(rs.campos, device).reshape(-1)
         if self.bg.numel() != 3 or self.view.numel() != 16 or self.proj.numel() != 16 or self.campos.numel() != 3:
             raise ValueError("bg/campos must have 3 elements and view/proj matrices 16")
+        B = _lib.Boundary(device)
         s = _lib.Settings()
         s.image_height, s.image_width = int(rs.image_height), int(rs.image_width)
         s.tanfovx, s.tanfovy = float(rs.tanfovx), float(rs.tanfovy)
-        s.bg, s.scale_modifier = self.bg.data_ptr(), float(rs.scale_modifier)
-        s.viewmatrix, s.projmatrix = self.view.data_ptr(), self.proj.data_ptr()
-        s.sh_degree, s.campos = int(rs.sh_degree), self.campos.data_ptr()
+        s.bg, s.scale_modifier = B.ptr(self.bg, "bg"), float(rs.scale_modifier)
+        s.viewmatrix, s.projmatrix = B.ptr(self.view, "viewmatrix"), B.ptr(self.proj, "projmatrix")
+        s.sh_degree, s.campos = int(rs.sh_degree), B.ptr(self.campos, "campos")
         s.prefiltered, s.debug = int(bool(rs.prefiltered)), int(bool(rs.debug))
         s.include_feature = int(bool(rs.include_feature))
         self.c = s
@@ -115,10 +108,6 @@ class RasterizerState:
         self.geom, self.binning, self.img = geom, binning, img
         self.num_rendered, self.radii = num_rendered, radii
         self.composited = False           # backward_composite_native ran (it may run once)
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class PendingForward:
@@ -193,11 +182,12 @@ def _fwd_inputs(means3D, opacities, shs, colors_precomp, language_feature, scale
     C = language_feature.shape[1] if language_feature is not None else 0
     fin = _lib.FwdIn()
     fin.P, fin.M, fin.C = P, M, C
-    fin.means3D, fin.shs, fin.colors_precomp = means3D.data_ptr(), _ptr(shs), _ptr(colors_precomp)
-    fin.language_feature, fin.opacities = _ptr(language_feature), opacities.data_ptr()
-    fin.scales, fin.rotations, fin.cov3D_precomp = _ptr(scales), _ptr(rotations), _ptr(cov3D_precomp)
     inputs = dict(means3D=means3D, opacities=opacities, shs=shs, colors_precomp=colors_precomp,
                   language_feature=language_feature, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
+    B = _lib.Boundary(device)
+    fin.means3D, fin.opacities = B.ptr(means3D, "means3D"), B.ptr(opacities, "opacities")
+    for name in ("shs", "colors_precomp", "language_feature", "scales", "rotations", "cov3D_precomp"):
+        setattr(fin, name, B.opt(inputs[name], name))
     return fin, inputs, P
 
 
@@ -214,7 +204,7 @@ def preprocess_native(raster_settings, means3D, opacities, shs=None, colors_prec
     host memory and PendingForward.resolve(binning) reads it later (render_native resolves too),
     so a caller can enqueue this view's preprocess ahead of another view's work on the same stream."""
     device = _check_device(means3D)
-    L = _lib.load()
+    L, B = _lib.load(), _lib.Boundary(device)
     stream = stream or torch.cuda.current_stream(device)
     st = _NativeSettings(raster_settings, device)
     fin, inputs, P = _fwd_inputs(means3D, opacities, shs, colors_precomp, language_feature, scales, rotations,
@@ -224,13 +214,12 @@ def preprocess_native(raster_settings, means3D, opacities, shs=None, colors_prec
         radii = torch.empty(P, dtype=torch.int32, device=device)
         geom = torch.empty(int(L.lsr_geom_bytes(P)), dtype=torch.uint8, device=device)
     fout = _lib.FwdOut()
-    fout.radii = radii.data_ptr()
+    fout.radii = B.ptr(radii, "radii", torch.int32)
     if defer_count:
         count = torch.zeros(2, dtype=torch.int32, pin_memory=True)
         _check_forward(L.lsr_forward_preprocess_async(ctypes.byref(st.c), ctypes.byref(fin), ctypes.byref(fout),
-                                                      ctypes.c_void_p(geom.data_ptr()),
-                                                      ctypes.c_void_p(count.data_ptr()),
-                                                      ctypes.c_void_p(stream.cuda_stream)),
+                                                      B.ptr(geom, "geom", torch.uint8),
+                                                      _lib.HOST.ptr(count, "count", torch.int32), B.stream(stream)),
                        "lsr_forward_preprocess_async", raster_settings, inputs)
         pf = PendingForward(raster_settings, st, fin, inputs, geom, radii, None, device, H, W)
         pf.count_host, pf.stream = count, stream
@@ -239,8 +228,7 @@ def preprocess_native(raster_settings, means3D, opacities, shs=None, colors_prec
         return pf
     K = ctypes.c_int64(0)
     _check_forward(L.lsr_forward_preprocess(ctypes.byref(st.c), ctypes.byref(fin), ctypes.byref(fout),
-                                            ctypes.c_void_p(geom.data_ptr()), ctypes.byref(K),
-                                            ctypes.c_void_p(stream.cuda_stream)),
+                                            B.ptr(geom, "geom", torch.uint8), ctypes.byref(K), B.stream(stream)),
                    "lsr_forward_preprocess", raster_settings, inputs)
     pf = PendingForward(raster_settings, st, fin, inputs, geom, radii, K.value, device, H, W)
     if binning:
@@ -250,7 +238,7 @@ def preprocess_native(raster_settings, means3D, opacities, shs=None, colors_prec
 
 def _run_binning(pf, stream):
     """lsr_forward_binning of a preprocessed view on `stream`; render_native's stream waits for it."""
-    L = _lib.load()
+    L, B = _lib.load(), _lib.Boundary(pf.device)
     device, H, W, K = pf.device, pf.H, pf.W, pf.num_rendered
     if _BINNING_DELAY_CYCLES:             # test hook: holds the binning back to expose missing waits
         with torch.cuda.stream(stream):
@@ -259,9 +247,9 @@ def _run_binning(pf, stream):
         pf.binning = torch.empty(int(L.lsr_binning_bytes(K)), dtype=torch.uint8, device=device)
         pf.img = torch.empty(int(L.lsr_img_bytes(W, H)), dtype=torch.uint8, device=device)
     _check_forward(L.lsr_forward_binning(ctypes.byref(pf.settings.c), ctypes.byref(pf.fin),
-                                         ctypes.c_void_p(pf.geom.data_ptr()), ctypes.c_void_p(pf.binning.data_ptr()),
-                                         ctypes.c_void_p(pf.img.data_ptr()), ctypes.c_int64(K),
-                                         ctypes.c_void_p(stream.cuda_stream)),
+                                         B.ptr(pf.geom, "geom", torch.uint8),
+                                         B.ptr(pf.binning, "binning", torch.uint8),
+                                         B.ptr(pf.img, "img", torch.uint8), ctypes.c_int64(K), B.stream(stream)),
                    "lsr_forward_binning", pf.raster_settings, pf.inputs)
     pf.ready = torch.cuda.Event()
     pf.ready.record(stream)               # render_native's stream waits for the binning
@@ -272,8 +260,8 @@ def language_split_native(language_feature, stream=None, out=None):
     """lsr_language_split: [P,32] fp32 -> [P,64] int16 holding the bf16 bit patterns (hi channels,
     then lo) that the compositors' matrix-core operands use; lsr_fwd_in.language_feature_split.
     `out` may be a preallocated [P,64] int16 tensor."""
-    L = _lib.load()
     device = _check_device(language_feature)
+    L, B = _lib.load(), _lib.Boundary(device)
     P, C = language_feature.shape
     stream = stream or torch.cuda.current_stream(device)
     lang = language_feature.detach().to(torch.float32).contiguous()
@@ -282,8 +270,8 @@ def language_split_native(language_feature, stream=None, out=None):
             out = torch.empty(P, 2 * C, dtype=torch.int16, device=device)
     elif out.shape != (P, 2 * C) or out.dtype != torch.int16 or not out.is_contiguous():
         raise ValueError("language_split_native: out must be a contiguous [P, 2C] int16 tensor")
-    _lib.check(L.lsr_language_split(P, C, ctypes.c_void_p(lang.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                    ctypes.c_void_p(stream.cuda_stream)), "lsr_language_split")
+    _lib.check(L.lsr_language_split(P, C, B.ptr(lang, "language_feature"), B.ptr(out, "out", torch.int16),
+                                    B.stream(stream)), "lsr_language_split")
     return out
 
 
@@ -320,7 +308,7 @@ def preprocess_views_native(raster_settings_list, means3D, opacities, shs=None, 
     instances by tile and sorts each bucket in LDS, lsr_forward_binning_views_tb).  Same lists, same
     results; the split into first views and order_stream views applies to the instance scans."""
     device = _check_device(means3D)
-    L = _lib.load()
+    L, B = _lib.load(), _lib.Boundary(device)
     stream = stream or torch.cuda.current_stream(device)
     fin, inputs, P = _fwd_inputs(means3D, opacities, shs, colors_precomp, language_feature, scales, rotations,
                                  cov3D_precomp)
@@ -336,7 +324,7 @@ def preprocess_views_native(raster_settings_list, means3D, opacities, shs=None, 
     if split:   # allocated now (fin carries the pointer), written behind the batch's count event
         with torch.cuda.stream(stream):
             inputs["language_feature_split"] = torch.empty(P, 64, dtype=torch.int16, device=device)
-        fin.language_feature_split = inputs["language_feature_split"].data_ptr()
+        fin.language_feature_split = B.ptr(inputs["language_feature_split"], "language_feature_split", torch.int16)
         # with row_chunks the language rows may still be arriving (each chunk's before() waits for
         # them): the split is then always enqueued behind the chunk loop
         if not split_behind_counts and not row_chunks:
@@ -349,11 +337,11 @@ def preprocess_views_native(raster_settings_list, means3D, opacities, shs=None, 
         geoms = [torch.empty(int(L.lsr_geom_bytes(P)), dtype=torch.uint8, device=device) for _ in range(n)]
     fouts = [_lib.FwdOut() for _ in range(n)]
     for fo, r in zip(fouts, radii):
-        fo.radii = r.data_ptr()
+        fo.radii = B.ptr(r, "radii", torch.int32)
     k = n if (order_first is None or order_stream is None) else max(0, min(int(order_first), n))
     counts = torch.zeros(k, 2, dtype=torch.int32, pin_memory=True) if k > 0 else None
-    s_arr, o_arr, g_arr = _settings_array(sts), _struct_array(_lib.FwdOut, fouts), _ptr_array(geoms)
-    fi, stp = ctypes.byref(fin), ctypes.c_void_p(stream.cuda_stream)
+    s_arr, o_arr, g_arr = _settings_array(sts), _struct_array(_lib.FwdOut, fouts), B.array(geoms, "geom", torch.uint8)
+    fi, stp = ctypes.byref(fin), B.stream(stream)
 
     def check(rc, what):
         _check_forward(rc, what, raster_settings_list[0], inputs)
@@ -370,10 +358,10 @@ def preprocess_views_native(raster_settings_list, means3D, opacities, shs=None, 
                 before()
             check(rows_fn(n, int(r0), int(r1), s_arr, fi, o_arr, g_arr, stp), rows_what)
         if k > 0:
-            check(count_fn(k, s_arr, fi, g_arr, ctypes.c_void_p(counts.data_ptr()), stp), count_what)
+            check(count_fn(k, s_arr, fi, g_arr, _lib.HOST.ptr(counts, "counts", torch.int32), stp), count_what)
     else:
         check(L.lsr_forward_preprocess_views_split_async(n, k, s_arr, fi, o_arr, g_arr,
-                                                         ctypes.c_void_p(counts.data_ptr() if k else 0), stp),
+                                                         _lib.HOST.opt(counts, "counts", torch.int32), stp),
               "lsr_forward_preprocess_views_split_async")
     ev = torch.cuda.Event()
     ev.record(stream)
@@ -383,8 +371,8 @@ def preprocess_views_native(raster_settings_list, means3D, opacities, shs=None, 
         for g in geoms[k:]:
             g.record_stream(order_stream)
         counts_b = torch.zeros(n - k, 2, dtype=torch.int32, pin_memory=True)
-        check(count_fn(n - k, _settings_array(sts[k:]), fi, _ptr_array(geoms[k:]), ctypes.c_void_p(counts_b.data_ptr()),
-                       ctypes.c_void_p(order_stream.cuda_stream)), count_what)
+        check(count_fn(n - k, _settings_array(sts[k:]), fi, B.array(geoms[k:], "geom", torch.uint8),
+                       _lib.HOST.ptr(counts_b, "counts", torch.int32), B.stream(order_stream)), count_what)
         ev_b = torch.cuda.Event()
         ev_b.record(order_stream)
         late = (counts_b, ev_b)
@@ -431,9 +419,11 @@ def _img_bytes(W, H):
 def _view_arrays(views, *between):
     """(settings array, &fin, *between, geom, binning, img and num_rendered arrays) of binned views
     (PendingForward or RasterizerState) of the same Gaussians: the *_views entry points' argument run."""
+    B = _lib.Boundary(views[0].geom.device)
     return (_settings_array([v.settings for v in views]), ctypes.byref(views[0].fin), *between,
-            _ptr_array([v.geom for v in views]), _ptr_array([v.binning for v in views]),
-            _ptr_array([v.img for v in views]), _int64_array([v.num_rendered for v in views]))
+            B.array([v.geom for v in views], "geom", torch.uint8),
+            B.array([v.binning for v in views], "binning", torch.uint8),
+            B.array([v.img for v in views], "img", torch.uint8), _int64_array([v.num_rendered for v in views]))
 
 
 def _forward_outputs(pf):
@@ -442,9 +432,11 @@ def _forward_outputs(pf):
     color = torch.empty(3, H, W, dtype=torch.float32, device=pf.device)
     lang_out = torch.empty(C, H, W, dtype=torch.float32, device=pf.device)
     depth = torch.empty(1, H, W, dtype=torch.float32, device=pf.device)
+    B = _lib.Boundary(pf.device)
     fout = _lib.FwdOut()
-    fout.out_color, fout.out_language_feature = color.data_ptr(), _ptr(lang_out) if C > 0 else None
-    fout.radii, fout.out_depth = pf.radii.data_ptr(), depth.data_ptr()
+    fout.out_color = B.ptr(color, "out_color")
+    fout.out_language_feature = B.ptr(lang_out, "out_language_feature") if C > 0 else None
+    fout.radii, fout.out_depth = B.ptr(pf.radii, "radii", torch.int32), B.ptr(depth, "out_depth")
     return color, lang_out, depth, fout
 
 
@@ -507,7 +499,7 @@ def binning_views_native(pendings, stream=None):
         off += sizes[2 * i + 1]
     fn, what = ((L.lsr_forward_binning_views_tb, "lsr_forward_binning_views_tb") if tb
                 else (L.lsr_forward_binning_views, "lsr_forward_binning_views"))
-    _check_forward(fn(n, *_view_arrays(pendings), ctypes.c_void_p(stream.cuda_stream)), what,
+    _check_forward(fn(n, *_view_arrays(pendings), _lib.Boundary(device).stream(stream)), what,
                    pendings[0].raster_settings, pendings[0].inputs)
     ev = torch.cuda.Event()
     ev.record(stream)
@@ -523,6 +515,7 @@ def render_native(pending: PendingForward):
         binning_views_native([pending], stream=torch.cuda.current_stream(pending.device))
     pending.resolve()
     device, H, W = pending.device, pending.H, pending.W
+    B = _lib.Boundary(device)
     stream = torch.cuda.current_stream(device)
     pending.geom.record_stream(stream)    # allocated on the preprocess stream, used from here on
     pending.radii.record_stream(stream)
@@ -540,8 +533,8 @@ def render_native(pending: PendingForward):
     fn, what = (L.lsr_forward_composite, "lsr_forward_composite") if binned else (L.lsr_forward_render,
                                                                                    "lsr_forward_render")
     _check_forward(fn(ctypes.byref(pending.settings.c), ctypes.byref(pending.fin), ctypes.byref(fout),
-                      ctypes.c_void_p(pending.geom.data_ptr()), ctypes.c_void_p(binning.data_ptr()),
-                      ctypes.c_void_p(img.data_ptr()), ctypes.c_int64(K), _stream(device)), what,
+                      B.ptr(pending.geom, "geom", torch.uint8), B.ptr(binning, "binning", torch.uint8),
+                      B.ptr(img, "img", torch.uint8), ctypes.c_int64(K), B.stream(stream)), what,
                    pending.raster_settings, pending.inputs)
     state = RasterizerState(pending.settings, pending.inputs, pending.fin, pending.geom, binning, img, K, pending.radii)
     return color, lang_out, pending.radii, depth, state
@@ -561,9 +554,9 @@ def radii_max_native(radii, out, accumulate=False, stream=None):
             raise ValueError("radii_max_native: int32 [P] tensors on out's device")
     if out.dtype != torch.int32 or not out.is_contiguous():
         raise ValueError("radii_max_native: out must be a contiguous int32 tensor")
-    stream = stream or torch.cuda.current_stream(out.device)
-    _lib.check(L.lsr_radii_max(P, len(rs), _ptr_array(rs), ctypes.c_void_p(out.data_ptr()), 1 if accumulate else 0,
-                               ctypes.c_void_p(stream.cuda_stream)), "lsr_radii_max")
+    B = _lib.Boundary(_check_device(out))
+    _lib.check(L.lsr_radii_max(P, len(rs), B.array(rs, "radii", torch.int32), B.ptr(out, "out", torch.int32),
+                               1 if accumulate else 0, B.stream(stream)), "lsr_radii_max")
     return out
 
 
@@ -593,7 +586,7 @@ def render_views_native(pendings):
         fouts.append(fout)
     _check_forward(L.lsr_forward_composite_views(len(pendings),
                                                  *_view_arrays(pendings, _struct_array(_lib.FwdOut, fouts)),
-                                                 _stream(device)),
+                                                 _lib.Boundary(device).stream(stream)),
                    "lsr_forward_composite_views", pendings[0].raster_settings, pendings[0].inputs)
     res = []
     for pf, (color, lang_out, depth) in zip(pendings, outs):
@@ -618,16 +611,17 @@ def backward_native(state: RasterizerState, grad_color, grad_lang=None, grad_dep
     (bitwise reproducible gradients).  Returns the dict of gradient tensors."""
     L = _lib.load()
     device = state.inputs["means3D"].device
+    B = _lib.Boundary(device)
     P, C = state.fin.P, state.fin.C
     g = _grad_buffers(state, out, accumulate, need or {})
     keep, gin = _bwd_in(state, grad_color, grad_lang, grad_depth, deterministic)   # keep: alive until enqueued
-    gout = _bwd_out(g)
+    gout = _bwd_out(g, B)
     scratch = torch.empty(int(L.lsr_backward_bytes(P, state.num_rendered, C, 1 if deterministic else 0)),
                           dtype=torch.uint8, device=device)
     rc = L.lsr_backward(ctypes.byref(state.settings.c), ctypes.byref(state.fin), ctypes.byref(gin), ctypes.byref(gout),
-                        ctypes.c_void_p(state.geom.data_ptr()), ctypes.c_void_p(state.binning.data_ptr()),
-                        ctypes.c_void_p(state.img.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
-                        ctypes.c_int64(state.num_rendered), ctypes.c_int32(1 if accumulate else 0), _stream(device))
+                        B.ptr(state.geom, "geom", torch.uint8), B.ptr(state.binning, "binning", torch.uint8),
+                        B.ptr(state.img, "img", torch.uint8), B.ptr(scratch, "scratch", torch.uint8),
+                        ctypes.c_int64(state.num_rendered), ctypes.c_int32(1 if accumulate else 0), B.stream())
     if rc != 0 and state.settings.c.debug:
         print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.")
         torch.save(dict(grad_color=keep[0].cpu()), "snapshot_bw.dump")
@@ -657,12 +651,12 @@ def backward_views_native(states, grad_colors, grad_langs=None, grad_depths=None
     for s in states[1:]:
         if s.inputs["means3D"].data_ptr() != inp["means3D"].data_ptr():
             raise ValueError("all views must render the same Gaussians")
-    device = inp["means3D"].device
+    B = _lib.Boundary(inp["means3D"].device)
     g = _grad_buffers(st0, out, accumulate, need or {})
     keeps, gins = _bwd_in_views(states, grad_colors, grad_langs, grad_depths)   # keeps: alive until enqueued
-    gout = _bwd_out(g)
+    gout = _bwd_out(g, B)
     _lib.check(L.lsr_backward_views(n, *_view_arrays(states, _struct_array(_lib.BwdIn, gins), ctypes.byref(gout)),
-                                    1 if accumulate else 0, _stream(device)), "lsr_backward_views")
+                                    1 if accumulate else 0, B.stream()), "lsr_backward_views")
     for s in states:
         s.composited = True
     return g
@@ -686,16 +680,17 @@ def backward_composite_native(state: RasterizerState, grad_color, grad_lang=None
     if state.composited:
         raise RuntimeError("backward_composite_native already ran on this forward: its screen-space sums are "
                            "accumulated in the forward's workspace, so a second run would double them")
-    device = state.inputs["means3D"].device
+    B = _lib.Boundary(state.inputs["means3D"].device)
     P, C = state.fin.P, state.fin.C
     keep, gi = _bwd_in(state, grad_color, grad_lang, grad_depth)
     if dL_dlanguage is not None and (dL_dlanguage.shape != (P, C) or not dL_dlanguage.is_contiguous()):
         raise ValueError("dL_dlanguage must be a contiguous [P, C] tensor")
     _lib.check(L.lsr_backward_composite(ctypes.byref(state.settings.c), ctypes.byref(state.fin), ctypes.byref(gi),
-                                        _ptr(dL_dlanguage if C > 0 else None), ctypes.c_void_p(state.geom.data_ptr()),
-                                        ctypes.c_void_p(state.binning.data_ptr()),
-                                        ctypes.c_void_p(state.img.data_ptr()),
-                                        ctypes.c_int64(state.num_rendered), _stream(device)), "lsr_backward_composite")
+                                        B.opt(dL_dlanguage if C > 0 else None, "dL_dlanguage"),
+                                        B.ptr(state.geom, "geom", torch.uint8),
+                                        B.ptr(state.binning, "binning", torch.uint8),
+                                        B.ptr(state.img, "img", torch.uint8),
+                                        ctypes.c_int64(state.num_rendered), B.stream()), "lsr_backward_composite")
     state.composited = True
     return CompositeGrad(state, keep)
 
@@ -714,7 +709,7 @@ def backward_composite_views_native(states, grad_colors, grad_langs=None, grad_d
             raise RuntimeError("backward_composite_native already ran on this forward: its screen-space sums are "
                                "accumulated in the forward's workspace, so a second run would double them")
     st0 = states[0]
-    device = st0.inputs["means3D"].device
+    B = _lib.Boundary(st0.inputs["means3D"].device)
     P, C = st0.fin.P, st0.fin.C
     if dL_dlanguage is not None and (dL_dlanguage.shape != (P, C) or not dL_dlanguage.is_contiguous()):
         raise ValueError("dL_dlanguage must be a contiguous [P, C] tensor")
@@ -724,8 +719,8 @@ def backward_composite_views_native(states, grad_colors, grad_langs=None, grad_d
     keeps, gins = _bwd_in_views(states, grad_colors, grad_langs, grad_depths)
     _lib.check(L.lsr_backward_composite_views(len(states),
                                               *_view_arrays(states, _struct_array(_lib.BwdIn, gins),
-                                                            _ptr(dL_dlanguage if C > 0 else None)),
-                                              _stream(device)), "lsr_backward_composite_views")
+                                                            B.opt(dL_dlanguage if C > 0 else None, "dL_dlanguage")),
+                                              B.stream()), "lsr_backward_composite_views")
     for s in states:
         s.composited = True
     return [CompositeGrad(s, k) for s, k in zip(states, keeps)]
@@ -749,16 +744,16 @@ def backward_preprocess_views_native(parts, out=None, accumulate=False, need=Non
     for p_ in parts[1:]:
         if p_.state.inputs["means3D"].data_ptr() != inp["means3D"].data_ptr():
             raise ValueError("all views must render the same Gaussians")
-    device = inp["means3D"].device
+    B = _lib.Boundary(inp["means3D"].device)
     need = dict(need or {})
     need["language_feature"] = False
     g = _grad_buffers(st0, out, accumulate, need)
-    gout = _bwd_out(g)
+    gout = _bwd_out(g, B)
     s_arr = _settings_array([p_.state.settings for p_ in parts])
-    geoms = _ptr_array([p_.state.geom for p_ in parts])
+    geoms = B.array([p_.state.geom for p_ in parts], "geom", torch.uint8)
     if row_chunks is None:
         _lib.check(L.lsr_backward_preprocess_views(n, s_arr, ctypes.byref(st0.fin), ctypes.byref(gout), geoms,
-                                                   1 if accumulate else 0, _stream(device)),
+                                                   1 if accumulate else 0, B.stream()),
                    "lsr_backward_preprocess_views")
     else:
         P = st0.fin.P
@@ -768,9 +763,9 @@ def backward_preprocess_views_native(parts, out=None, accumulate=False, need=Non
                 raise ValueError(f"row_chunks must tile [0, {P}) in order, got {list(row_chunks)}")
             expect = r1
             part = {k: (v[r0:r1] if v is not None else None) for k, v in g.items()}
-            gc = _bwd_out(part)
+            gc = _bwd_out(part, B)
             _lib.check(L.lsr_backward_preprocess_views_rows(n, s_arr, ctypes.byref(st0.fin), ctypes.byref(gc), geoms,
-                                                            1 if accumulate else 0, r0, r1 - r0, _stream(device)),
+                                                            1 if accumulate else 0, r0, r1 - r0, B.stream()),
                        "lsr_backward_preprocess_views_rows")
             if on_rows is not None:
                 on_rows(r0, r1)
@@ -815,8 +810,10 @@ def _bwd_in(state, grad_color, grad_lang, grad_depth, deterministic=False):
         torch.zeros(3, H, W, dtype=torch.float32, device=device)
     gl = grad_lang.detach().to(torch.float32).contiguous() if (grad_lang is not None and state.fin.C > 0) else None
     gd = grad_depth.detach().to(torch.float32).contiguous() if grad_depth is not None else None
+    B = _lib.Boundary(device)
     gin = _lib.BwdIn()
-    gin.dL_dout_color, gin.dL_dout_language_feature, gin.dL_dout_depth = gc.data_ptr(), _ptr(gl), _ptr(gd)
+    gin.dL_dout_color, gin.dL_dout_language_feature = B.ptr(gc, "grad_color"), B.opt(gl, "grad_lang")
+    gin.dL_dout_depth = B.opt(gd, "grad_depth")
     gin.deterministic = 1 if deterministic else 0
     return (gc, gl, gd), gin
 
@@ -829,12 +826,13 @@ def _bwd_in_views(states, grad_colors, grad_langs, grad_depths):
     return [k for k, _ in pairs], [gi for _, gi in pairs]
 
 
-def _bwd_out(g):
+def _bwd_out(g, B):
     gout = _lib.BwdOut()
-    gout.dL_dmeans3D, gout.dL_dmeans2D, gout.dL_dcolors = _ptr(g["means3D"]), _ptr(g["means2D"]), _ptr(g["colors"])
-    gout.dL_dlanguage_feature, gout.dL_dopacity = _ptr(g["language_feature"]), _ptr(g["opacities"])
-    gout.dL_dcov3D, gout.dL_dsh = _ptr(g["cov3D"]), _ptr(g["sh"])
-    gout.dL_dscales, gout.dL_drotations = _ptr(g["scales"]), _ptr(g["rotations"])
+    for field, name in (("dL_dmeans3D", "means3D"), ("dL_dmeans2D", "means2D"), ("dL_dcolors", "colors"),
+                        ("dL_dlanguage_feature", "language_feature"), ("dL_dopacity", "opacities"),
+                        ("dL_dcov3D", "cov3D"), ("dL_dsh", "sh"), ("dL_dscales", "scales"),
+                        ("dL_drotations", "rotations")):
+        setattr(gout, field, B.opt(g[name], name))
     return gout
 
 
@@ -975,9 +973,10 @@ class GaussianRasterizer(nn.Module):
             proj = _f32(rs.projmatrix, positions.device).reshape(-1)
             out = torch.empty(pos.shape[0], dtype=torch.uint8, device=positions.device)
             L = _lib.load()
-            _lib.check(L.lsr_mark_visible(pos.shape[0], ctypes.c_void_p(pos.data_ptr()), ctypes.c_void_p(view.data_ptr()),
-                                          ctypes.c_void_p(proj.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                          _stream(positions.device)), "lsr_mark_visible")
+            B = _lib.Boundary(_check_device(positions))
+            _lib.check(L.lsr_mark_visible(pos.shape[0], B.ptr(pos, "positions"), B.ptr(view, "viewmatrix"),
+                                          B.ptr(proj, "projmatrix"), B.ptr(out, "out", torch.uint8), B.stream()),
+                       "lsr_mark_visible")
             return out.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, language_feature_precomp=None,

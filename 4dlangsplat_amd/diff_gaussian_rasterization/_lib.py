@@ -1,5 +1,6 @@
 """ctypes binding of liblsr.so (include/lsr.h).  No torch types cross the boundary: only device
-pointers, sizes and the HIP stream handle.
+pointers, sizes and the HIP stream handle.  Boundary (below) is the one place a tensor becomes such a
+pointer: no other module of the package calls .data_ptr() for an argument or a struct field.
 
 The library is built in-tree (4dlangsplat_amd/csrc/Makefile -> 4dlangsplat_amd/build/liblsr.so).
 There is no fallback: if the library is missing, importing the rasterizer raises.
@@ -8,6 +9,8 @@ from __future__ import annotations
 
 import ctypes
 import os
+
+import torch
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("LSR_LIBRARY", os.path.join(_PKG, "build", "liblsr.so"))
@@ -383,6 +386,67 @@ def load():
             raise ImportError(f"{path}: {lib.lsr_last_error().decode()} (rebuild it: make -C 4dlangsplat_amd/csrc)")
         _LIB = lib
     return _LIB
+
+
+class Boundary:
+    """What may cross into liblsr.so for a call that runs on `device`: the address of a contiguous tensor of
+    the dtype the C side reads, on that device, and a stream of that device.  Anything else raises ValueError
+    before an address is taken; ok() is the same test as a bool, for the callers that fall back to torch.
+    Nothing is converted, copied or allocated here, and no device guard is entered.  ptr / opt / array return bare
+    integers that keep nothing alive: the caller holds the tensor until the call is enqueued, so a copy made for the
+    call (.contiguous(), .to()) is bound to a name first, never written inside the boundary's argument."""
+    __slots__ = ("device",)
+
+    def __init__(self, device):
+        if not isinstance(device, torch.device):
+            device = torch.device(device)
+        if device.type == "cuda" and device.index is None:   # "cuda": the current device, as torch places tensors
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device = device    # with its index, as tensor.device gives it
+
+    def ok(self, t, dtype=torch.float32, strided=False) -> bool:
+        return (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == self.device
+                and (strided or t.is_contiguous()))
+
+    def ptr(self, t, name="tensor", dtype=torch.float32, strided=False) -> int:
+        """The address of `t`.  strided=True is for the entry points that take the tensor's strides as arguments of
+        their own: the caller passes them, so `t` need not be contiguous."""
+        if not self.ok(t, dtype, strided):
+            raise ValueError(f"{name}: {'' if strided else 'contiguous '}{_short(dtype)} tensor on {self.device} "
+                             f"required, got {_found(t)}")
+        return t.data_ptr()
+
+    def opt(self, t, name="tensor", dtype=torch.float32):
+        """ptr(), or None (NULL) for None"""
+        return None if t is None else self.ptr(t, name, dtype)
+
+    def array(self, tensors, name="tensors", dtype=torch.float32):
+        """(c_void_p * n) over the addresses of `tensors`, each checked as `name[i]`"""
+        for i, t in enumerate(tensors):
+            if not self.ok(t, dtype):
+                self.ptr(t, f"{name}[{i}]", dtype)   # raises, naming the element
+        return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+    def stream(self, stream=None):
+        """the native calls' stream argument: `stream` (a torch stream of this device) or the device's current one"""
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        elif stream.device != self.device:
+            raise ValueError(f"stream: a stream of {self.device} required, got one of {stream.device}")
+        return ctypes.c_void_p(stream.cuda_stream)
+
+
+HOST = Boundary(torch.device("cpu"))   # for the pinned host buffers a native call writes its counts to
+
+
+def _short(dtype):
+    return str(dtype).replace("torch.", "")
+
+
+def _found(t):
+    if not isinstance(t, torch.Tensor):
+        return type(t).__name__
+    return f"{'' if t.is_contiguous() else 'non-contiguous '}{_short(t.dtype)} on {t.device}"
 
 
 def check(rc: int, what: str):

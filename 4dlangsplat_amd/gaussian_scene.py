@@ -282,6 +282,16 @@ def read_ply_vertices(path: str) -> Dict[str, np.ndarray]:
 
 
 # ---- render(): gaussian_renderer/__init__.py:19-248 -----------------------------------------------
+def _native(*tensors) -> bool:
+    """float32 tensors on one CUDA device, of any strides: what activate / repeat_views / split_views hand to their
+    native launches (made contiguous there, then confirmed by the same boundary); anything else takes the PyTorch ops."""
+    from diff_gaussian_rasterization import _lib
+    if not (isinstance(tensors[0], torch.Tensor) and tensors[0].is_cuda):
+        return False
+    B = _lib.Boundary(tensors[0].device)
+    return all(B.ok(t, strided=True) for t in tensors)
+
+
 class _Activate(torch.autograd.Function):
     """exp(scales), normalize(rotations), sigmoid(opacity) (gaussian_renderer/__init__.py:191-193) in one
     launch forward and one backward (lsr_activate / lsr_activate_backward, include/lsr_train.h)
@@ -290,30 +300,30 @@ class _Activate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, s_raw, r_raw, o_raw):
         from diff_gaussian_rasterization import _lib
-        L = _lib.load()
         s_raw, r_raw, o_raw = s_raw.contiguous(), r_raw.contiguous(), o_raw.contiguous()
-        if s_raw.dtype != torch.float32 or r_raw.shape[-1] != 4 or s_raw.shape[-1] != 3 \
+        if not _native(s_raw, r_raw, o_raw) or r_raw.shape[-1] != 4 or s_raw.shape[-1] != 3 \
                 or not (s_raw.shape[0] == r_raw.shape[0] == o_raw.shape[0]) or o_raw.numel() != o_raw.shape[0]:
             raise ValueError("activate: float32 scales [N,3], rotations [N,4], opacity [N,1]")
         s, r, o = torch.empty_like(s_raw), torch.empty_like(r_raw), torch.empty_like(o_raw)
-        p = lambda t: t.data_ptr()   # noqa: E731
-        st = torch.cuda.current_stream(s_raw.device).cuda_stream
-        _lib.check(L.lsr_activate(s_raw.shape[0], p(s_raw), p(r_raw), p(o_raw), p(s), p(r), p(o), st), "lsr_activate")
+        B = _lib.Boundary(s_raw.device)
+        _lib.check(_lib.load().lsr_activate(s_raw.shape[0], B.ptr(s_raw, "scales"), B.ptr(r_raw, "rotations"),
+                                            B.ptr(o_raw, "opacity"), B.ptr(s, "scales out"), B.ptr(r, "rotations out"),
+                                            B.ptr(o, "opacity out"), B.stream()), "lsr_activate")
         ctx.save_for_backward(s, r_raw, o)
         return s, r, o
 
     @staticmethod
     def backward(ctx, ds, dr, do):
         from diff_gaussian_rasterization import _lib
-        L = _lib.load()
         s, r_raw, o = ctx.saved_tensors
         need = ctx.needs_input_grad
+        B = _lib.Boundary(s.device)
         outs = [torch.empty_like(x) if need[k] else None for k, x in enumerate((s, r_raw, o))]
-        g = [None if x is None else x.contiguous() for x in (ds, dr, do)]
-        p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-        st = torch.cuda.current_stream(s.device).cuda_stream
-        _lib.check(L.lsr_activate_backward(s.shape[0], p(s), p(r_raw), p(o), p(g[0]), p(g[1]), p(g[2]),
-                                           p(outs[0]), p(outs[1]), p(outs[2]), st), "lsr_activate_backward")
+        keep = [None if x is None else x.contiguous() for x in (ds, dr, do)]   # alive until the launch is enqueued
+        g = [B.opt(x, name) for x, name in zip(keep, ("grad scales", "grad rotations", "grad opacity"))]
+        _lib.check(_lib.load().lsr_activate_backward(s.shape[0], B.ptr(s, "scales"), B.ptr(r_raw, "rotations"),
+                                                     B.ptr(o, "opacity"), *g, *[B.opt(x, "grad out") for x in outs],
+                                                     B.stream()), "lsr_activate_backward")
         return tuple(outs)
 
 
@@ -322,11 +332,11 @@ class _RepeatViews(torch.autograd.Function):
     summed) in one (lsr_repeat_rows / lsr_sum_row_blocks, include/lsr_train.h)."""
 
     @staticmethod
-    def _jobs(pairs):
+    def _jobs(B, pairs):
         from diff_gaussian_rasterization import _lib
         rows = (_lib.RowTensor * len(pairs))()
         for k, (src, dst) in enumerate(pairs):
-            rows[k].src, rows[k].dst = src.data_ptr(), dst.data_ptr()
+            rows[k].src, rows[k].dst = B.ptr(src, f"tensor {k}"), B.ptr(dst, f"result {k}")
             rows[k].row_bytes, rows[k].zero_from = src[0].numel() * 4 if src.shape[0] else 4, 0
         return rows
 
@@ -335,13 +345,13 @@ class _RepeatViews(torch.autograd.Function):
         from diff_gaussian_rasterization import _lib
         xs = [x.contiguous() for x in xs]
         P = xs[0].shape[0]
-        if any(x.dtype != torch.float32 or x.shape[0] != P for x in xs):
-            raise ValueError("repeat_views: float32 tensors of the same row count")
+        if not _native(*xs) or any(x.shape[0] != P for x in xs):
+            raise ValueError("repeat_views: float32 tensors of the same row count on one CUDA device")
         outs = [x.new_empty((V * P,) + tuple(x.shape[1:])) for x in xs]
-        ctx.V, ctx.P, ctx.shapes = V, P, [tuple(x.shape) for x in xs]
-        st = torch.cuda.current_stream(xs[0].device).cuda_stream
-        _lib.check(_lib.load().lsr_repeat_rows(len(xs), _RepeatViews._jobs(list(zip(xs, outs))), P, V, st),
-                   "lsr_repeat_rows")
+        ctx.V, ctx.P, ctx.shapes, ctx.device = V, P, [tuple(x.shape) for x in xs], xs[0].device
+        B = _lib.Boundary(ctx.device)
+        jobs = _RepeatViews._jobs(B, list(zip(xs, outs)))
+        _lib.check(_lib.load().lsr_repeat_rows(len(xs), jobs, P, V, B.stream()), "lsr_repeat_rows")
         return tuple(outs)
 
     @staticmethod
@@ -357,9 +367,9 @@ class _RepeatViews(torch.autograd.Function):
             pairs.append((g.contiguous(), d))
             grads.append(d)
         if pairs:
-            st = torch.cuda.current_stream(pairs[0][0].device).cuda_stream
-            _lib.check(_lib.load().lsr_sum_row_blocks(len(pairs), _RepeatViews._jobs(pairs), ctx.P, ctx.V, st),
-                       "lsr_sum_row_blocks")
+            B = _lib.Boundary(ctx.device)   # the forward's device: the gradients are confirmed against it
+            jobs = _RepeatViews._jobs(B, pairs)
+            _lib.check(_lib.load().lsr_sum_row_blocks(len(pairs), jobs, ctx.P, ctx.V, B.stream()), "lsr_sum_row_blocks")
         return (None,) + tuple(grads)
 
 
@@ -382,7 +392,7 @@ class _SplitViews(torch.autograd.Function):
     @staticmethod
     def forward(ctx, V, *xs):
         P = xs[0].shape[0] // V
-        ctx.V, ctx.P, ctx.shapes = V, P, [tuple(x.shape) for x in xs]
+        ctx.V, ctx.P, ctx.shapes, ctx.device = V, P, [tuple(x.shape) for x in xs], xs[0].device
         ctx.set_materialize_grads(False)   # absent view gradients stay None (no zero tensors made)
         outs = []
         for x in xs:
@@ -394,6 +404,7 @@ class _SplitViews(torch.autograd.Function):
         from diff_gaussian_rasterization import _lib
         V, P = ctx.V, ctx.P
         res, jobs, keep = [], [], []
+        B = _lib.Boundary(ctx.device)   # the forward's device: the gradients are confirmed against it
         for k, shp in enumerate(ctx.shapes):
             part = gs[k * V:(k + 1) * V]
             if not ctx.needs_input_grad[1 + k] or all(g is None for g in part):
@@ -403,13 +414,13 @@ class _SplitViews(torch.autograd.Function):
             out = ref.new_empty(shp)
             res.append(out)
             row = out[0].numel() * 4
-            for b, g in enumerate(part):
+            for g, dst in zip(part, out.split(P)):   # dst: the view's row block of out
                 src = _zeros_source(out.device, P * row) if g is None else g.contiguous()
                 keep.append(src)
-                jobs.append((src.data_ptr(), out.data_ptr() + b * P * row, row))
+                jobs.append((B.ptr(src, f"gradient {k}"), B.ptr(dst, f"result {k}"), row))
         if not jobs:
             return (None,) + tuple(res)
-        st = torch.cuda.current_stream(next(r for r in res if r is not None).device).cuda_stream
+        st = B.stream()
         L = _lib.load()
         for i in range(0, len(jobs), 32):
             chunk = jobs[i:i + 32]
@@ -423,7 +434,7 @@ class _SplitViews(torch.autograd.Function):
 def split_views(V, *xs):
     """xs' row blocks per view (tuples of V views each); on the GPU the backward is one launch."""
     live = [x for x in xs if x is not None]
-    if not live or not live[0].is_cuda or live[0].shape[0] == 0:
+    if not live or not _native(*live) or live[0].shape[0] == 0:
         return [x.split(x.shape[0] // V) if x is not None else (None,) * V for x in xs]
     parts = iter(_SplitViews.apply(V, *live))
     return [tuple(next(parts) for _ in range(V)) if x is not None else (None,) * V for x in xs]
@@ -431,15 +442,16 @@ def split_views(V, *xs):
 
 def repeat_views(V, *xs):
     """The tensors' rows repeated V times (render_views): one native launch each way on the GPU."""
-    if xs[0].is_cuda and xs[0].shape[0] > 0:
+    if _native(*xs) and xs[0].shape[0] > 0:
         return _RepeatViews.apply(V, *xs)
     return tuple(x.repeat(V, *([1] * (x.dim() - 1))) for x in xs)
 
 
 def activate(scales, rotations, opacity):
-    """The render path's activations: one native launch each way on the GPU (_Activate); the PyTorch
-    ops for host tensors or a missing input."""
-    if scales is not None and rotations is not None and scales.is_cuda:
+    """The render path's activations: one native launch each way on the GPU (_Activate) for float32 inputs on
+    one CUDA device; the PyTorch ops otherwise (host tensors, another dtype, a missing input).  Those ops are
+    independent, so inputs on different devices come back activated where they were: nothing is moved or raised."""
+    if scales is not None and rotations is not None and _native(scales, rotations, opacity):
         return _Activate.apply(scales, rotations, opacity)
     return (torch.exp(scales) if scales is not None else None,
             torch.nn.functional.normalize(rotations) if rotations is not None else None, torch.sigmoid(opacity))

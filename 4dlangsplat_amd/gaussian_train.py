@@ -20,7 +20,6 @@ positions and scales.  There is no CPU fallback: liblsr.so and a GPU are require
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, Iterable, Optional
 
 import numpy as np
@@ -49,14 +48,6 @@ def get_expon_lr_func(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, ma
     return helper
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
 class GaussianTrainer:
     """Optimizer + densification state over raw Gaussian tensors (a GaussianScene's, or a dict).
 
@@ -79,8 +70,11 @@ class GaussianTrainer:
             if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
                 raise ValueError(f"{n}: contiguous float32 CUDA tensor required")
             dev = t.device if dev is None else dev
+            if t.device != dev:
+                raise ValueError(f"{n}: on {t.device}, the other parameters on {dev}")
             self.params[n] = t.detach().requires_grad_(True)
         self.device = dev
+        self._B = _lib.Boundary(dev)
         P = self.P
         for n, t in self.params.items():
             if t.shape[0] != P:
@@ -123,24 +117,25 @@ class GaussianTrainer:
     # ---- optimizer (train.py:420-421) -------------------------------------------------------
     def step(self):
         """One torch.optim.Adam step over every group with a gradient: one kernel launch."""
-        groups = []
+        groups, B = [], self._B
         for n, p in self.params.items():
             if n not in self.lrs or p.grad is None:
                 continue
             g = p.grad
-            if not g.is_contiguous() or g.dtype != torch.float32 or g.shape != p.shape:
-                raise ValueError(f"{n}: gradient must be a contiguous float32 tensor of the parameter's shape")
-            self.steps[n] += 1
+            if g.shape != p.shape:
+                raise ValueError(f"{n}: gradient of shape {tuple(g.shape)}, parameter {tuple(p.shape)}")
             ag = _lib.AdamGroup()
-            ag.param, ag.grad = p.data_ptr(), g.data_ptr()
-            ag.exp_avg, ag.exp_avg_sq = self.exp_avg[n].data_ptr(), self.exp_avg_sq[n].data_ptr()
+            ag.param, ag.grad = B.ptr(p, n), B.ptr(g, n + ".grad")
+            ag.exp_avg = B.ptr(self.exp_avg[n], n + ".exp_avg")
+            ag.exp_avg_sq = B.ptr(self.exp_avg_sq[n], n + ".exp_avg_sq")
+            self.steps[n] += 1
             ag.n, ag.lr, ag.step = p.numel(), float(self.lrs[n]), self.steps[n]
             groups.append(ag)
         if not groups:
             return
         arr = (_lib.AdamGroup * len(groups))(*groups)
-        _lib.check(self._L.lsr_adam_step(arr, len(groups), self.betas[0], self.betas[1], self.eps,
-                                         _stream(self.device)), "lsr_adam_step")
+        _lib.check(self._L.lsr_adam_step(arr, len(groups), self.betas[0], self.betas[1], self.eps, B.stream()),
+                   "lsr_adam_step")
 
     def zero_grad(self, set_to_none=True):
         for p in self.params.values():
@@ -157,12 +152,14 @@ class GaussianTrainer:
         g = viewspace_point_grad.detach()
         if g.dim() != 2 or g.shape[0] != P or g.shape[1] < 2 or g.stride(1) != 1 or g.dtype != torch.float32:
             raise ValueError("viewspace_point_grad must be float32 [P, >=2] with unit column stride")
-        r = radii.to(torch.int32).contiguous()
+        r = radii.to(self.device, torch.int32).contiguous()
         if r.shape != (P,):
             raise ValueError("radii must be [P]")
-        _lib.check(self._L.lsr_densify_stats(P, _ptr(r), _ptr(g), g.stride(0), _ptr(self.max_radii2D),
-                                             _ptr(self.xyz_gradient_accum), _ptr(self.denom), _stream(self.device)),
-                   "lsr_densify_stats")
+        B = self._B   # g may be a column slice: the kernel takes its row stride
+        args = (P, B.ptr(r, "radii", torch.int32), B.ptr(g, "viewspace_point_grad", strided=True), g.stride(0),
+                B.ptr(self.max_radii2D, "max_radii2D"), B.ptr(self.xyz_gradient_accum, "xyz_gradient_accum"),
+                B.ptr(self.denom, "denom"), B.stream())
+        _lib.check(self._L.lsr_densify_stats(*args), "lsr_densify_stats")
 
     # ---- row surgery -------------------------------------------------------------------------
     def _workspace(self, P):
@@ -177,7 +174,7 @@ class GaussianTrainer:
             shape = (n_rows,) + tuple(src.shape[1:])
             dst = torch.empty(shape, dtype=src.dtype, device=self.device)
             rt = _lib.RowTensor()
-            rt.src, rt.dst = src.data_ptr(), dst.data_ptr()
+            rt.src, rt.dst = self._B.ptr(src, key[1], src.dtype), self._B.ptr(dst, key[1], src.dtype)
             rt.row_bytes = int(np.prod(shape[1:], dtype=np.int64)) * src.element_size()
             rt.zero_from = zf
             jobs.append(rt)
@@ -196,8 +193,8 @@ class GaussianTrainer:
         if len(jobs) > _lib.GATHER_MAX_TENSORS:
             raise ValueError("too many row tensors for one gather launch")
         arr = (_lib.RowTensor * len(jobs))(*jobs)
-        _lib.check(self._L.lsr_gather_rows(len(jobs), arr, _ptr(index), n_rows, _stream(self.device)),
-                   "lsr_gather_rows")
+        _lib.check(self._L.lsr_gather_rows(len(jobs), arr, self._B.ptr(index, "index", torch.int32), n_rows,
+                                           self._B.stream()), "lsr_gather_rows")
         return new
 
     def _install(self, new):
@@ -223,11 +220,12 @@ class GaussianTrainer:
                 raise ValueError(f"densify needs the {n} group")
         index = torch.empty((N + 1) * max(P, 1), dtype=torch.int32, device=self.device)
         counts = torch.zeros(3, dtype=torch.int64, device=self.device)
-        ws = self._workspace(P)
-        _lib.check(self._L.lsr_densify_plan(P, _ptr(self.xyz_gradient_accum), _ptr(self.denom),
-                                            _ptr(self.params["scaling"]), float(max_grad), float(self.percent_dense),
-                                            float(extent), N, _ptr(index), _ptr(counts), _ptr(ws),
-                                            _stream(self.device)), "lsr_densify_plan")
+        ws, B = self._workspace(P), self._B
+        _lib.check(self._L.lsr_densify_plan(P, B.ptr(self.xyz_gradient_accum, "xyz_gradient_accum"),
+                                            B.ptr(self.denom, "denom"), B.ptr(self.params["scaling"], "scaling"),
+                                            float(max_grad), float(self.percent_dense), float(extent), N,
+                                            B.ptr(index, "index", torch.int32), B.ptr(counts, "counts", torch.int64),
+                                            B.ptr(ws, "workspace", torch.uint8), B.stream()), "lsr_densify_plan")
         kept, n_clone, n_split = (int(x) for x in counts.cpu())
         n_rows = kept + n_clone + N * n_split
         old = {n: self.params[n].detach() for n in ("xyz", "scaling", "rotation")}
@@ -238,10 +236,12 @@ class GaussianTrainer:
             samples = samples.to(self.device, torch.float32).contiguous()
             if samples.shape != (N * n_split, 3):
                 raise ValueError(f"samples must be [{N * n_split}, 3]")
-            _lib.check(self._L.lsr_split_fixup(N * n_split, kept + n_clone, N, _ptr(index), _ptr(old["xyz"]),
-                                               _ptr(old["scaling"]), _ptr(old["rotation"]), _ptr(samples),
-                                               _ptr(new[("p", "xyz")]), _ptr(new[("p", "scaling")]),
-                                               _stream(self.device)), "lsr_split_fixup")
+            _lib.check(self._L.lsr_split_fixup(N * n_split, kept + n_clone, N, B.ptr(index, "index", torch.int32),
+                                               B.ptr(old["xyz"], "xyz"), B.ptr(old["scaling"], "scaling"),
+                                               B.ptr(old["rotation"], "rotation"), B.ptr(samples, "samples"),
+                                               B.ptr(new[("p", "xyz")], "new xyz"),
+                                               B.ptr(new[("p", "scaling")], "new scaling"), B.stream()),
+                       "lsr_split_fixup")
         self._install(new)
         return n_clone, n_split
 
@@ -251,11 +251,13 @@ class GaussianTrainer:
         P = self.P
         index = torch.empty(max(P, 1), dtype=torch.int32, device=self.device)
         counts = torch.zeros(1, dtype=torch.int64, device=self.device)
-        ws = self._workspace(P)
-        _lib.check(self._L.lsr_prune_plan(P, _ptr(self.params["opacity"]), _ptr(self.max_radii2D),
-                                          _ptr(self.params["scaling"]), float(min_opacity),
-                                          float(max_screen_size or 0.0), float(extent), _ptr(index), _ptr(counts),
-                                          _ptr(ws), _stream(self.device)), "lsr_prune_plan")
+        ws, B = self._workspace(P), self._B
+        _lib.check(self._L.lsr_prune_plan(P, B.ptr(self.params["opacity"], "opacity"),
+                                          B.ptr(self.max_radii2D, "max_radii2D"),
+                                          B.ptr(self.params["scaling"], "scaling"), float(min_opacity),
+                                          float(max_screen_size or 0.0), float(extent),
+                                          B.ptr(index, "index", torch.int32), B.ptr(counts, "counts", torch.int64),
+                                          B.ptr(ws, "workspace", torch.uint8), B.stream()), "lsr_prune_plan")
         kept = int(counts.cpu()[0])
         self._install(self._gather(index, kept, zero_from=kept, stats_keep=True))
         return P - kept
@@ -268,8 +270,10 @@ class GaussianTrainer:
         skips it)."""
         n = "opacity"
         self.params[n].grad = None
-        _lib.check(self._L.lsr_reset_opacity(self.P, _ptr(self.params[n]), _ptr(self.exp_avg[n]),
-                                             _ptr(self.exp_avg_sq[n]), _stream(self.device)), "lsr_reset_opacity")
+        B = self._B
+        _lib.check(self._L.lsr_reset_opacity(self.P, B.ptr(self.params[n], n), B.ptr(self.exp_avg[n], "exp_avg"),
+                                             B.ptr(self.exp_avg_sq[n], "exp_avg_sq"), B.stream()),
+                   "lsr_reset_opacity")
 
     def state_rows(self) -> Iterable[str]:
         return tuple(self.params)
@@ -360,22 +364,22 @@ class TensorAdam:
         self.steps[n] = int(float(entry["step"]))
 
     def step(self, grads: Dict[str, torch.Tensor]):
-        groups = []
+        groups, B = [], _lib.Boundary(next(iter(self.params.values())).device)
         for n, p in self.params.items():
             g = grads.get(n)
             if g is None or n not in self.lr:
                 continue
-            if g.shape != p.shape or not g.is_contiguous() or not p.is_contiguous():
-                raise ValueError(f"{n}: gradient and parameter must be contiguous and of one shape")
-            self.steps[n] += 1
+            if g.shape != p.shape:
+                raise ValueError(f"{n}: gradient of shape {tuple(g.shape)}, parameter {tuple(p.shape)}")
             ag = _lib.AdamGroup()
-            ag.param, ag.grad = p.data_ptr(), g.data_ptr()
-            ag.exp_avg, ag.exp_avg_sq = self.exp_avg[n].data_ptr(), self.exp_avg_sq[n].data_ptr()
+            ag.param, ag.grad = B.ptr(p, n), B.ptr(g, n + ".grad")
+            ag.exp_avg = B.ptr(self.exp_avg[n], n + ".exp_avg")
+            ag.exp_avg_sq = B.ptr(self.exp_avg_sq[n], n + ".exp_avg_sq")
+            self.steps[n] += 1
             ag.n, ag.lr, ag.step = p.numel(), float(self.lr[n]), self.steps[n]
             groups.append(ag)
-        dev = next(iter(self.params.values())).device
         for i in range(0, len(groups), _lib.ADAM_MAX_GROUPS):
             chunk = groups[i:i + _lib.ADAM_MAX_GROUPS]
             arr = (_lib.AdamGroup * len(chunk))(*chunk)
-            _lib.check(self._L.lsr_adam_step(arr, len(chunk), self.betas[0], self.betas[1], self.eps, _stream(dev)),
+            _lib.check(self._L.lsr_adam_step(arr, len(chunk), self.betas[0], self.betas[1], self.eps, B.stream()),
                        "lsr_adam_step")

@@ -18,7 +18,6 @@ the reference's does).  Zero padding of n // 2; channels are independent planes;
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from typing import Optional, Sequence, Tuple
 
@@ -86,20 +85,15 @@ def native_eligible(images: Sequence[torch.Tensor], gt: torch.Tensor, window_siz
     x0 = images[0]
     if not (x0.is_cuda and x0.dim() == 3 and x0.numel() > 0):
         return False
-    for x in images:
-        if x.dtype != torch.float32 or x.device != x0.device or x.shape != x0.shape or not x.is_contiguous():
-            return False
-    if gt.dtype != torch.float32 or gt.device != x0.device or gt.requires_grad or gt.dim() != 4:
+    from diff_gaussian_rasterization import _lib
+    B = _lib.Boundary(x0.device)   # the test _ImageLossViews' addresses are taken under
+    if not all(B.ok(x) and x.shape == x0.shape for x in images):
         return False
-    if gt.shape[0] != len(images) or gt.shape[1:] != x0.shape:
+    if gt.requires_grad or gt.dim() != 4 or gt.shape[0] != len(images) or gt.shape[1:] != x0.shape:
         return False
-    if not all(gt[v].is_contiguous() for v in range(gt.shape[0])):
+    if not all(B.ok(y) for y in gt):
         return False
     return len(images) == 1 or gt.stride(0) >= x0.numel()
-
-
-def _pointers(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
 class _ImageLossViews(torch.autograd.Function):
@@ -113,6 +107,7 @@ class _ImageLossViews(torch.autograd.Function):
         L = _lib.load()
         V, (C, H, W) = len(images), images[0].shape
         dev = images[0].device
+        B = _lib.Boundary(dev)
         nbytes = int(L.lsr_image_loss_workspace_bytes(V, C, H, W))
         if nbytes < 0:
             raise ValueError(L.lsr_last_error().decode())
@@ -121,9 +116,9 @@ class _ImageLossViews(torch.autograd.Function):
         totals = torch.empty(2, dtype=torch.float32, device=dev)
         stride = gt.stride(0) if V > 1 else C * H * W
         with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(L.lsr_image_loss_views(V, C, H, W, _pointers(images), gt.data_ptr(), stride, stats.data_ptr(),
-                                              totals.data_ptr(), ws.data_ptr(), st), "lsr_image_loss_views")
+            _lib.check(L.lsr_image_loss_views(V, C, H, W, B.array(images, "images"), B.ptr(gt[0], "gt"), stride,
+                                              B.ptr(stats, "stats"), B.ptr(totals, "totals"),
+                                              B.ptr(ws, "workspace", torch.uint8), B.stream()), "lsr_image_loss_views")
         ctx.stride = stride
         ctx.set_materialize_grads(False)                 # an unused output's gradient arrives as None: NULL
         ctx.save_for_backward(gt, ws, *images)
@@ -137,14 +132,14 @@ class _ImageLossViews(torch.autograd.Function):
         gt, ws, *images = ctx.saved_tensors
         V, (C, H, W) = len(images), images[0].shape
         dev = images[0].device
+        B = _lib.Boundary(dev)
         grads = [torch.empty_like(x) for x in images]
         keep = [None if g is None else g.to(device=dev, dtype=torch.float32).contiguous() for g in (g_l1, g_ssim)]
-        ptr = [None if g is None else g.data_ptr() for g in keep]
         with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
             _lib.check(_lib.load().lsr_image_loss_views_backward(
-                V, C, H, W, _pointers(images), gt.data_ptr(), ctx.stride, ptr[0], ptr[1], _pointers(grads),
-                ws.data_ptr(), st), "lsr_image_loss_views_backward")
+                V, C, H, W, B.array(images, "images"), B.ptr(gt[0], "gt"), ctx.stride, B.opt(keep[0], "grad l1"),
+                B.opt(keep[1], "grad ssim"), B.array(grads, "grads"), B.ptr(ws, "workspace", torch.uint8),
+                B.stream()), "lsr_image_loss_views_backward")
         return (None,) + tuple(grads)
 
 

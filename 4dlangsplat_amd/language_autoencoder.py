@@ -49,6 +49,11 @@ def _bn_key(i):
     return f"encoder.{3 * i - 2}"
 
 
+def _c_dtype(t):
+    """What the library reads a state-dict tensor as: float32, num_batches_tracked int64."""
+    return torch.float32 if t.is_floating_point() else torch.int64
+
+
 def _dec_key(j):
     return f"decoder.{2 * j}"          # a ReLU sits between the Linear layers
 
@@ -191,22 +196,25 @@ class LanguageAutoencoder:
     def native_ok(self):
         """Inside include/lsr_autoencoder.h's limits, float32 (the counts int64), on one CUDA device."""
         hidden = self.encoder_dims[:-1] + self.decoder_dims + [self.feature_dim]
-        ts = list(self.sd.values())
+        B = _lib.Boundary(self.device)
         return (self.n_enc <= _lib.AE_MAX_LAYERS and self.n_dec <= _lib.AE_MAX_LAYERS
                 and all(x % 16 == 0 and 16 <= x <= _lib.AE_MAX_WIDTH for x in hidden)
                 and 1 <= self.latent_dim <= _lib.AE_MAX_LATENT and self.decoder_dims[-1] == self.feature_dim
-                and all(t.device.type == "cuda" and t.device == ts[0].device and t.is_contiguous()
-                        and t.dtype == (torch.float32 if t.is_floating_point() else torch.int64) for t in ts))
+                and self.device.type == "cuda" and all(B.ok(t, _c_dtype(t)) for t in self.sd.values()))
 
     def _params_struct(self, tensors):
         """lsr_ae_params of a dict with the parameter keys (the parameters, or one of Adam's moments)."""
-        s = _lib.AeParams()
+        s, B = _lib.AeParams(), _lib.Boundary(self.device)
+
+        def ptr(k):
+            return B.ptr(tensors[k], k)
+
         for i in range(self.n_enc):
-            s.enc_w[i], s.enc_b[i] = tensors[f"{_enc_key(i)}.weight"].data_ptr(), tensors[f"{_enc_key(i)}.bias"].data_ptr()
+            s.enc_w[i], s.enc_b[i] = ptr(f"{_enc_key(i)}.weight"), ptr(f"{_enc_key(i)}.bias")
             if i:
-                s.bn_w[i], s.bn_b[i] = tensors[f"{_bn_key(i)}.weight"].data_ptr(), tensors[f"{_bn_key(i)}.bias"].data_ptr()
+                s.bn_w[i], s.bn_b[i] = ptr(f"{_bn_key(i)}.weight"), ptr(f"{_bn_key(i)}.bias")
         for j in range(self.n_dec):
-            s.dec_w[j], s.dec_b[j] = tensors[f"{_dec_key(j)}.weight"].data_ptr(), tensors[f"{_dec_key(j)}.bias"].data_ptr()
+            s.dec_w[j], s.dec_b[j] = ptr(f"{_dec_key(j)}.weight"), ptr(f"{_dec_key(j)}.bias")
         return s
 
     def _struct(self):
@@ -219,10 +227,11 @@ class LanguageAutoencoder:
             for j, d in enumerate(self.decoder_dims):
                 s.dec_dims[j] = d
             s.p = self._params_struct(self.sd)
+            B = _lib.Boundary(self.device)
             for i in range(1, self.n_enc):
-                s.bn_mean[i] = self.sd[f"{_bn_key(i)}.running_mean"].data_ptr()
-                s.bn_var[i] = self.sd[f"{_bn_key(i)}.running_var"].data_ptr()
-                s.bn_count[i] = self.sd[f"{_bn_key(i)}.num_batches_tracked"].data_ptr()
+                s.bn_mean[i] = B.ptr(self.sd[f"{_bn_key(i)}.running_mean"], "running_mean")
+                s.bn_var[i] = B.ptr(self.sd[f"{_bn_key(i)}.running_var"], "running_var")
+                s.bn_count[i] = B.ptr(self.sd[f"{_bn_key(i)}.num_batches_tracked"], "num_batches_tracked", torch.int64)
             self._struct_cache = s
         return self._struct_cache
 
@@ -233,7 +242,7 @@ class LanguageAutoencoder:
         return torch.empty(n, dtype=torch.uint8, device=self.device), n
 
     def _takes_native(self, x):
-        return x.dtype == torch.float32 and x.device.type == "cuda" and self.native_ok() and x.device == self.device
+        return x.dtype == torch.float32 and x.device == self.device and self.native_ok()
 
     def _check_rows(self, x):
         if x.shape[-1] != self.feature_dim:
@@ -296,9 +305,10 @@ class LanguageAutoencoder:
         if flat.shape[0]:
             with torch.cuda.device(x.device):
                 ws, n = self._workspace(flat.shape[0], False)
-                _lib.check(_lib.load().lsr_ae_encode(ctypes.byref(self._struct()), flat.shape[0], flat.data_ptr(),
-                                                     out.data_ptr(), ws.data_ptr(), n,
-                                                     torch.cuda.current_stream(x.device).cuda_stream), "lsr_ae_encode")
+                B = _lib.Boundary(x.device)
+                _lib.check(_lib.load().lsr_ae_encode(ctypes.byref(self._struct()), flat.shape[0], B.ptr(flat, "rows"),
+                                                     B.ptr(out, "out"), B.ptr(ws, "workspace", torch.uint8), n,
+                                                     B.stream()), "lsr_ae_encode")
         return out.reshape(*x.shape[:-1], self.latent_dim)
 
     def decoder(self):
@@ -325,9 +335,11 @@ class LanguageAutoencoder:
             sums = torch.empty(2, dtype=torch.float64, device=x.device)
             with torch.cuda.device(x.device):
                 ws, nb = self._workspace(n, False)
-                _lib.check(_lib.load().lsr_ae_eval_loss(ctypes.byref(self._struct()), n, x.data_ptr(), sums.data_ptr(),
-                                                        ws.data_ptr(), nb,
-                                                        torch.cuda.current_stream(x.device).cuda_stream), "lsr_ae_eval_loss")
+                B = _lib.Boundary(x.device)
+                _lib.check(_lib.load().lsr_ae_eval_loss(ctypes.byref(self._struct()), n, B.ptr(x, "rows"),
+                                                        B.ptr(sums, "sums", torch.float64),
+                                                        B.ptr(ws, "workspace", torch.uint8), nb, B.stream()),
+                           "lsr_ae_eval_loss")
             sq, cs = sums[0], sums[1]
         else:
             sq, cs = self._loss_sums_torch(x)
@@ -382,18 +394,18 @@ class AutoencoderTrainer:
         return l2.detach(), cos.detach()
 
     def _step_native(self, x):
-        ae, B = self.ae, x.shape[0]
+        ae, rows, B = self.ae, x.shape[0], _lib.Boundary(x.device)
         if self._structs is None:
             self._structs = (ae._params_struct(self.exp_avg), ae._params_struct(self.exp_avg_sq))
-        if B not in self._ws:
-            self._ws[B] = ae._workspace(B, True)
-        ws, n = self._ws[B]
+        if rows not in self._ws:
+            self._ws[rows] = ae._workspace(rows, True)
+        ws, n = self._ws[rows]
         losses = torch.empty(2, dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             _lib.check(_lib.load().lsr_ae_train_step(
-                ctypes.byref(ae._struct()), ctypes.byref(self._structs[0]), ctypes.byref(self._structs[1]), B,
-                x.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps, self.t, self.cos_weight,
-                losses.data_ptr(), ws.data_ptr(), n, torch.cuda.current_stream(x.device).cuda_stream), "lsr_ae_train_step")
+                ctypes.byref(ae._struct()), ctypes.byref(self._structs[0]), ctypes.byref(self._structs[1]), rows,
+                B.ptr(x, "batch"), self.lr, self.betas[0], self.betas[1], self.eps, self.t, self.cos_weight,
+                B.ptr(losses, "losses"), B.ptr(ws, "workspace", torch.uint8), n, B.stream()), "lsr_ae_train_step")
         return losses[0], losses[1]
 
     def step(self, batch):

@@ -29,14 +29,6 @@ from deformation import COFF, HEADS, LANG_DISCRETE, LANG_NORESNET, LANG_RESIDUAL
 from diff_gaussian_rasterization import _lib
 
 
-def _vp(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _device_f32(t, name: str) -> torch.Tensor:
     if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32:
         raise ValueError(f"{name}: a float32 CUDA tensor is required")
@@ -49,6 +41,12 @@ def _outputs(P: int, k: int, D: int, device):
             torch.empty(P, device=device), torch.empty(P, dtype=torch.int32, device=device))
 
 
+def _out_ptrs(B, outs):
+    centers, counts, inertia, iters = outs
+    return (B.ptr(centers, "centers"), B.ptr(counts, "counts", torch.int32), B.ptr(inertia, "inertia"),
+            B.ptr(iters, "iters", torch.int32))
+
+
 @torch.no_grad()
 def kmeans_rows(x: torch.Tensor, k: int, max_iter: int = 100):
     """k-means of every row of x [P, S, D] (float32, CUDA) with the algorithm of include/lsr_centers.h.
@@ -57,9 +55,10 @@ def kmeans_rows(x: torch.Tensor, k: int, max_iter: int = 100):
     if x.dim() != 3:
         raise ValueError("x: [P, S, D]")
     P, S, D = x.shape
-    centers, counts, inertia, iters = _outputs(P, k, D, x.device)
-    _lib.check(_lib.load().lsr_centers_kmeans(_vp(x), P, S, D, int(k), int(max_iter), _vp(centers), _vp(counts),
-                                              _vp(inertia), _vp(iters), _stream(x.device)), "lsr_centers_kmeans")
+    centers, counts, inertia, iters = outs = _outputs(P, k, D, x.device)
+    B = _lib.Boundary(x.device)
+    _lib.check(_lib.load().lsr_centers_kmeans(B.ptr(x, "x"), P, S, D, int(k), int(max_iter), *_out_ptrs(B, outs),
+                                              B.stream()), "lsr_centers_kmeans")
     return centers, counts, inertia, iters
 
 
@@ -87,13 +86,14 @@ def sample_centers(field: DeformationField, lang: torch.Tensor, k: int = 3, samp
         times = _device_f32(times, "times")
         if tuple(times.shape) != (P, S):
             raise ValueError(f"times: [{P}, {S}]")
-    centers, counts, inertia, iters = _outputs(P, k, D, lang.device)
+    centers, counts, inertia, iters = outs = _outputs(P, k, D, lang.device)
+    B = _lib.Boundary(lang.device)
     xs = torch.empty(P, max(S, 0), D, device=lang.device) if debug else None
     ts = torch.empty(P, max(S, 0), device=lang.device) if debug else None
     _lib.check(_lib.load().lsr_centers_from_field(
-        ctypes.byref(field.net), _vp(field.workspace), P, _vp(lang), _vp(times), int(seed) & 0xFFFFFFFF, S, int(k),
-        int(max_iter), _vp(centers), _vp(counts), _vp(inertia), _vp(iters), _vp(xs), _vp(ts), _stream(lang.device)),
-        "lsr_centers_from_field")
+        ctypes.byref(field.net), B.ptr(field.workspace, "field.workspace", torch.uint8), P, B.ptr(lang, "lang"),
+        B.opt(times, "times"), int(seed) & 0xFFFFFFFF, S, int(k), int(max_iter), *_out_ptrs(B, outs),
+        B.opt(xs, "samples"), B.opt(ts, "sample times"), B.stream()), "lsr_centers_from_field")
     return (centers, counts, inertia, iters) + ((xs, ts) if debug else ())
 
 

@@ -109,19 +109,19 @@ class LanguageDecoder:
     def native_ok(self):
         """Inside the library's limits (include/lsr_query.h), float32, on one CUDA device."""
         d = self.dims
-        ts = self.weights + self.biases
+        B = _lib.Boundary(self.device)
         return (len(self.weights) <= _lib.QUERY_MAX_LAYERS and 1 <= d[0] <= _lib.QUERY_MAX_INPUT
                 and all(x % 16 == 0 and 16 <= x <= _lib.QUERY_MAX_WIDTH for x in d[1:])
-                and all(t.dtype == torch.float32 and t.device.type == "cuda" and t.device == ts[0].device for t in ts))
+                and self.device.type == "cuda" and all(B.ok(t) for t in self.weights + self.biases))
 
     def _struct(self):
-        s = _lib.Decoder()
+        s, B = _lib.Decoder(), _lib.Boundary(self.device)
         s.n_layers = len(self.weights)
         for i, x in enumerate(self.dims):
             s.dims[i] = x
         for i, (w, b) in enumerate(zip(self.weights, self.biases)):
-            s.weight[i] = w.data_ptr()
-            s.bias[i] = b.data_ptr()
+            s.weight[i] = B.ptr(w, f"decoder weight {i}")
+            s.bias[i] = B.ptr(b, f"decoder bias {i}")
         return s
 
     def _check_input(self, x):
@@ -147,10 +147,9 @@ class LanguageDecoder:
         out = torch.empty(flat.shape[0], self.d_out, dtype=torch.float32, device=x.device)
         if flat.shape[0]:
             with torch.cuda.device(x.device):
-                stream = torch.cuda.current_stream(x.device).cuda_stream
-                dec = self._struct()
-                _lib.check(_lib.load().lsr_query_decode(ctypes.byref(dec), flat.shape[0], flat.data_ptr(), self.c_in, 1,
-                                                        out.data_ptr(), stream), "lsr_query_decode")
+                dec, B = self._struct(), _lib.Boundary(x.device)
+                _lib.check(_lib.load().lsr_query_decode(ctypes.byref(dec), flat.shape[0], B.ptr(flat, "latent"),
+                                                        self.c_in, 1, B.ptr(out, "out"), B.stream()), "lsr_query_decode")
         return out.reshape(*x.shape[:-1], self.d_out)
 
 
@@ -196,10 +195,10 @@ def relevancy(latent, decoder, pos_embeds, neg_embeds, layout="hwc", scale=10.0)
         out = torch.empty(L, n_pos, H * W, dtype=torch.float32, device=latent.device)
         if H * W:
             pos, neg = pos_embeds.detach().contiguous(), neg_embeds.detach().contiguous()
-            lib, dec = _lib.load(), decoder._struct()
+            lib, dec, B = _lib.load(), decoder._struct(), _lib.Boundary(latent.device)
             chunk = _lib.QUERY_MAX_PHRASES - n_neg            # positives of one launch
             with torch.cuda.device(latent.device):
-                stream = torch.cuda.current_stream(latent.device).cuda_stream
+                stream = B.stream()
                 for l in range(L):
                     x = levels[l]
                     if H > 1 and W > 1 and x.stride(0) != W * x.stride(1):   # the pixels must share one stride
@@ -207,10 +206,10 @@ def relevancy(latent, decoder, pos_embeds, neg_embeds, layout="hwc", scale=10.0)
                     pix_stride = x.stride(1) if W > 1 else x.stride(0)
                     for p0 in range(0, n_pos, chunk):
                         n = min(chunk, n_pos - p0)
-                        _lib.check(lib.lsr_query_relevancy(ctypes.byref(dec), H * W, x.data_ptr(), pix_stride,
-                                                           x.stride(2), n, pos[p0:].data_ptr(), n_neg, neg.data_ptr(),
-                                                           float(scale), out[l, p0:].data_ptr(), stream),
-                                   "lsr_query_relevancy")
+                        _lib.check(lib.lsr_query_relevancy(ctypes.byref(dec), H * W, B.ptr(x, "latent", strided=True),
+                                                           pix_stride, x.stride(2), n, B.ptr(pos[p0:], "pos_embeds"),
+                                                           n_neg, B.ptr(neg, "neg_embeds"), float(scale),
+                                                           B.ptr(out[l, p0:], "out"), stream), "lsr_query_relevancy")
     out = out.reshape(L, n_pos, H, W)
     return out if latent.dim() == 4 else out[0]
 
@@ -341,12 +340,13 @@ def segment(rel, gt_masks=None, thresh=0.4, scale=29, strategy="point"):
             inter = torch.empty(M, dtype=torch.int64, device=dev)
             union = torch.empty(M, dtype=torch.int64, device=dev)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        ptr = lambda t: None if t is None else t.data_ptr()
+        B, u8, i64 = _lib.Boundary(dev), torch.uint8, torch.int64
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.lsr_segment(M, H, W, maps.data_ptr(), scale, float(thresh), _lib.SEGMENT_STRATEGIES[strategy],
-                                       ptr(gt8), n_pos, b.data_ptr(), raw8.data_ptr(), mask8.data_ptr(),
-                                       score.data_ptr(), ptr(inter), ptr(union), ws.data_ptr(), stream), "lsr_segment")
+            _lib.check(lib.lsr_segment(M, H, W, B.ptr(maps, "rel"), scale, float(thresh),
+                                       _lib.SEGMENT_STRATEGIES[strategy], B.opt(gt8, "gt_masks", u8), n_pos,
+                                       B.ptr(b, "blended"), B.ptr(raw8, "mask_raw", u8), B.ptr(mask8, "mask", u8),
+                                       B.ptr(score, "score"), B.opt(inter, "inter", i64), B.opt(union, "union", i64),
+                                       B.ptr(ws, "workspace", u8), B.stream()), "lsr_segment")
         raw, mask = raw8.view(torch.bool), mask8.view(torch.bool)
     shape = (L, n_pos)
     b, raw, mask, score = b.reshape(*shape, H, W), raw.reshape(*shape, H, W), mask.reshape(*shape, H, W), score.reshape(shape)
@@ -471,11 +471,11 @@ class LanguagePCA:
         if isinstance(frames, collections.abc.Iterator):      # one shot: it cannot be walked again
             frames = list(frames)
         lib = _lib.load()
-        C = dev = ws = sums = gram = None
+        C = dev = ws = sums = gram = B = None
         count = total = 0
 
         def sweeps():
-            """(index, frame, geometry, n_pix, workspace pointer) of every frame, checked against the first."""
+            """(index, frame pointer, geometry, n_pix, workspace pointer) of every frame, checked against the first."""
             nonlocal ws
             for i, f in enumerate(frames):
                 g = _pca_frame(f, layout)
@@ -486,19 +486,21 @@ class LanguagePCA:
                 need = lib.lsr_pca_workspace_bytes(g[0], n)
                 if ws is None or ws.numel() < need:
                     ws = torch.empty(need, dtype=torch.uint8, device=f.device)
-                yield i, f.detach(), g, n, ws.data_ptr()
+                Bf = B or _lib.Boundary(f.device)
+                yield i, Bf.ptr(f.detach(), f"frame {i}", strided=True), g, n, Bf.ptr(ws, "workspace", torch.uint8)
 
-        first = True
+        first, f64 = True, torch.float64
         for i, f, g, n, wp in sweeps():
             if C is None:
-                C, dev = g[0], f.device
+                C, dev = g[0], ws.device
+                B = _lib.Boundary(dev)
                 acc = torch.empty(_lib.PCA_MAX_CHANNELS * (_lib.PCA_MAX_CHANNELS + 1), dtype=torch.float64, device=dev)
                 sums, gram = acc[:_lib.PCA_MAX_CHANNELS], acc[_lib.PCA_MAX_CHANNELS:]
             count, total = i + 1, total + n
             if n:                                             # an empty frame launches nothing
                 with torch.cuda.device(dev):
-                    _lib.check(lib.lsr_pca_sums(C, n, f.data_ptr(), g[3], g[4], int(first), sums.data_ptr(), wp,
-                                                torch.cuda.current_stream(dev).cuda_stream), "lsr_pca_sums")
+                    _lib.check(lib.lsr_pca_sums(C, n, f, g[3], g[4], int(first), B.ptr(sums, "sums", f64), wp, B.stream()),
+                               "lsr_pca_sums")
                 first = False
         if not count:
             raise ValueError("fit() needs at least one frame")
@@ -510,18 +512,19 @@ class LanguagePCA:
         rng = torch.empty(2, dtype=torch.float32, device=dev)
         y = None
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
+            stream = B.stream()
             first, seen = True, 0
             for i, f, g, n, wp in sweeps():
                 seen += n
                 if n:
-                    _lib.check(lib.lsr_pca_gram(C, n, f.data_ptr(), g[3], g[4], sums.data_ptr(), total, int(first),
-                                                gram.data_ptr(), wp, stream), "lsr_pca_gram")
+                    _lib.check(lib.lsr_pca_gram(C, n, f, g[3], g[4], B.ptr(sums, "sums", f64), total, int(first),
+                                                B.ptr(gram, "gram", f64), wp, stream), "lsr_pca_gram")
                     first = False
             if seen != total:
                 raise ValueError(f"the frames changed between two walks of fit(): {total} pixels, then {seen}")
-            _lib.check(lib.lsr_pca_basis(C, total, sums.data_ptr(), gram.data_ptr(), mean.data_ptr(), comps.data_ptr(),
-                                         evals.data_ptr(), stream), "lsr_pca_basis")
+            _lib.check(lib.lsr_pca_basis(C, total, B.ptr(sums, "sums", f64), B.ptr(gram, "gram", f64),
+                                         B.ptr(mean, "mean"), B.ptr(comps, "components"), B.ptr(evals, "variance"),
+                                         stream), "lsr_pca_basis")
             first = True
             for i, f, g, n, wp in sweeps():
                 if not n:
@@ -529,9 +532,9 @@ class LanguagePCA:
                 last = keep_y and i == count - 1
                 if last:
                     y = torch.empty(n, 3, dtype=torch.float32, device=dev)
-                _lib.check(lib.lsr_pca_project(C, n, f.data_ptr(), g[3], g[4], mean.data_ptr(), comps.data_ptr(),
-                                               int(first), y.data_ptr() if last else None, rng.data_ptr(), wp, stream),
-                           "lsr_pca_project")
+                _lib.check(lib.lsr_pca_project(C, n, f, g[3], g[4], B.ptr(mean, "mean"), B.ptr(comps, "components"),
+                                               int(first), B.ptr(y, "y") if last else None, B.ptr(rng, "range"), wp,
+                                               stream), "lsr_pca_project")
                 first = False
         self.mean, self.components, self.explained_variance, self.range = mean, comps, evals, rng
         self.n_channels, self.n_samples = C, total
@@ -543,9 +546,10 @@ class LanguagePCA:
         lib = _lib.load()
         fn, what = ((lib.lsr_pca_colorize_u8, "lsr_pca_colorize_u8") if out == "uint8"
                     else (lib.lsr_pca_colorize_f32, "lsr_pca_colorize_f32"))
+        B = _lib.Boundary(dev)
         with torch.cuda.device(dev):
-            _lib.check(fn(H * W, y.data_ptr(), self.range.data_ptr(), img.data_ptr(),
-                          torch.cuda.current_stream(dev).cuda_stream), what)
+            _lib.check(fn(H * W, B.ptr(y, "y"), B.ptr(self.range, "range"), B.ptr(img, "image", img.dtype), B.stream()),
+                       what)
         return img
 
     @torch.no_grad()
@@ -563,10 +567,11 @@ class LanguagePCA:
         dev, n = frame.device, H * W
         y = torch.empty(n, 3, dtype=torch.float32, device=dev)
         if n:                                                 # y alone: no range is taken, so no workspace either
+            B = _lib.Boundary(dev)
             with torch.cuda.device(dev):
-                _lib.check(_lib.load().lsr_pca_project(C, n, frame.detach().data_ptr(), ps, cs, self.mean.data_ptr(),
-                                                       self.components.data_ptr(), 0, y.data_ptr(), None, None,
-                                                       torch.cuda.current_stream(dev).cuda_stream), "lsr_pca_project")
+                _lib.check(_lib.load().lsr_pca_project(C, n, B.ptr(frame.detach(), "frame", strided=True), ps, cs,
+                                                       B.ptr(self.mean, "mean"), B.ptr(self.components, "components"),
+                                                       0, B.ptr(y, "y"), None, None, B.stream()), "lsr_pca_project")
         return self._colorize(y, H, W, out)
 
 

@@ -135,12 +135,13 @@ def _fallback(images, sups, lam, beta, addcosloss):
     return loss
 
 
-def _views(imgs, grads, sups):
+def _views(B, imgs, grads, sups):
     from diff_gaussian_rasterization import _lib
     arr = (_lib.SegView * len(imgs))()
     for v, (x, s) in enumerate(zip(imgs, sups)):
-        arr[v].image, arr[v].seg, arr[v].table, arr[v].n_seg = x.data_ptr(), s.seg.data_ptr(), s.table.data_ptr(), s.n_seg
-        arr[v].d_image = grads[v].data_ptr() if grads is not None else None
+        arr[v].image, arr[v].n_seg = B.ptr(x, f"images[{v}]"), s.n_seg
+        arr[v].seg, arr[v].table = B.ptr(s.seg, f"seg {v}", torch.int32), B.ptr(s.table, f"table {v}")
+        arr[v].d_image = B.ptr(grads[v], f"grads[{v}]") if grads is not None else None
     return arr
 
 
@@ -155,15 +156,16 @@ class _SegLoss(torch.autograd.Function):
         imgs = [x.contiguous() for x in images]
         V, (C, H, W) = len(imgs), imgs[0].shape
         dev = imgs[0].device
+        B = _lib.Boundary(dev)
         nbytes = int(L.lsr_seg_loss_workspace_bytes(V, C, H, W))
         if nbytes < 0:
             raise ValueError(L.lsr_last_error().decode())
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
-            _lib.check(L.lsr_seg_loss_views(V, C, H, W, _views(imgs, None, sups), lam, beta, int(with_cos),
-                                            loss.data_ptr(), ws.data_ptr(), st), "lsr_seg_loss_views")
+            _lib.check(L.lsr_seg_loss_views(V, C, H, W, _views(B, imgs, None, sups), lam, beta, int(with_cos),
+                                            B.ptr(loss, "loss"), B.ptr(ws, "workspace", torch.uint8), B.stream()),
+                       "lsr_seg_loss_views")
         ctx.sups, ctx.scalars = sups, (lam, beta, int(with_cos))
         ctx.save_for_backward(ws, *imgs)
         return loss
@@ -177,10 +179,11 @@ class _SegLoss(torch.autograd.Function):
         dev = imgs[0].device
         grads = [torch.empty_like(x) for x in imgs]
         g = g.to(device=dev, dtype=torch.float32).contiguous()
-        st = torch.cuda.current_stream(dev).cuda_stream
+        B = _lib.Boundary(dev)
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().lsr_seg_loss_views_backward(V, C, H, W, _views(imgs, grads, ctx.sups), lam, beta,
-                                                               with_cos, g.data_ptr(), ws.data_ptr(), st),
+            _lib.check(_lib.load().lsr_seg_loss_views_backward(V, C, H, W, _views(B, imgs, grads, ctx.sups), lam, beta,
+                                                               with_cos, B.ptr(g, "grad"),
+                                                               B.ptr(ws, "workspace", torch.uint8), B.stream()),
                        "lsr_seg_loss_views_backward")
         return (None, None, None, None) + tuple(grads)
 
@@ -191,11 +194,10 @@ def native_eligible(images, sups) -> bool:
     x0 = images[0]
     if not (1 <= len(images) <= MAX_NATIVE_VIEWS and x0.is_cuda):
         return False
-    for x, s in zip(images, sups):
-        if x.dtype != torch.float32 or x.device != x0.device or s.seg.device != x0.device \
-                or s.table.device != x0.device or s.seg.dtype != torch.int32 or s.table.dtype != torch.float32:
-            return False
-    return True
+    from diff_gaussian_rasterization import _lib
+    B = _lib.Boundary(x0.device)   # the images are confirmed once _SegLoss has made them contiguous
+    return all(x.dtype == torch.float32 and x.device == x0.device and B.ok(s.seg, torch.int32) and B.ok(s.table)
+               for x, s in zip(images, sups))
 
 
 def segment_lang_loss(images: Sequence[torch.Tensor], sups: Sequence[SegmentSupervision], lam: float = 0.2,

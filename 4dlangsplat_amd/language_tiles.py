@@ -134,8 +134,11 @@ def _prepare_torch(image, label_maps):
 def native_eligible(image, label_maps) -> bool:
     """Whether prepare_frame tries the HIP path: a uint8 image and int32 label maps on one CUDA device.
     (Labels above 1023 are found by the census itself, which then hands the frame to the fallback.)"""
-    return bool(image.is_cuda and label_maps.device == image.device and image.dtype == torch.uint8
-                and label_maps.dtype == torch.int32)
+    if not image.is_cuda:
+        return False
+    from diff_gaussian_rasterization import _lib
+    B = _lib.Boundary(image.device)   # any strides: _prepare_native makes both contiguous, then takes their addresses
+    return B.ok(image, torch.uint8, strided=True) and B.ok(label_maps, torch.int32, strided=True)
 
 
 def _prepare_native(image, label_maps) -> Optional[FrameTiles]:
@@ -144,6 +147,7 @@ def _prepare_native(image, label_maps) -> Optional[FrameTiles]:
     lib = _lib.load()
     L, H, W = label_maps.shape
     dev = image.device
+    B, u8, i32 = _lib.Boundary(dev), torch.uint8, torch.int32
     image, label_maps = image.contiguous(), label_maps.contiguous()
     nbytes = int(lib.lsr_tiles_workspace_size(L))
     if nbytes < 0:
@@ -152,11 +156,11 @@ def _prepare_native(image, label_maps) -> Optional[FrameTiles]:
     desc = torch.empty((_lib.TILES_MAX_TILES, _lib.TILES_DESC_INTS), dtype=torch.int32, device=dev)
     counts = torch.zeros(_lib.TILES_COUNTS, dtype=torch.int32, pin_memory=True)
     stream = torch.cuda.current_stream(dev)
-    st = stream.cuda_stream
+    st, maps, wp = B.stream(stream), B.ptr(label_maps, "label_maps", i32), B.ptr(ws, "workspace", u8)
     with torch.cuda.device(dev):
-        _lib.check(lib.lsr_tiles_census(L, H, W, label_maps.data_ptr(), nbytes, ws.data_ptr(), st), "lsr_tiles_census")
-        _lib.check(lib.lsr_tiles_plan(L, H, W, nbytes, ws.data_ptr(), desc.data_ptr(), counts.data_ptr(), st),
-                   "lsr_tiles_plan")
+        _lib.check(lib.lsr_tiles_census(L, H, W, maps, nbytes, wp, st), "lsr_tiles_census")
+        _lib.check(lib.lsr_tiles_plan(L, H, W, nbytes, wp, B.ptr(desc, "desc", i32),
+                                      _lib.HOST.ptr(counts, "counts", i32), st), "lsr_tiles_plan")
         stream.synchronize()                                   # the frame's one host read
         got = counts.tolist()
         if got[L]:
@@ -166,9 +170,9 @@ def _prepare_native(image, label_maps) -> Optional[FrameTiles]:
         n = sum(lengths)
         seg = torch.empty((L, H, W), dtype=torch.int32, device=dev)
         tiles = torch.empty((n, 3, SIDE, SIDE), dtype=torch.float32, device=dev)
-        _lib.check(lib.lsr_tiles_render(L, H, W, label_maps.data_ptr(), image.data_ptr(), nbytes, ws.data_ptr(),
-                                        desc.data_ptr(), (ctypes.c_int32 * L)(*lengths), n, seg.data_ptr(),
-                                        tiles.data_ptr(), st), "lsr_tiles_render")
+        _lib.check(lib.lsr_tiles_render(L, H, W, maps, B.ptr(image, "image", u8), nbytes, wp, B.ptr(desc, "desc", i32),
+                                        (ctypes.c_int32 * L)(*lengths), n, B.ptr(seg, "seg", i32),
+                                        B.ptr(tiles, "tiles"), st), "lsr_tiles_render")
     d = desc[:n]
     return FrameTiles(tiles, seg, lengths, d[:, 1].clone(), d[:, 2:6].clone())
 

@@ -22,7 +22,6 @@ what the tests hold against the reference's results.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Mapping, Optional, Sequence, Tuple
 
 import torch
@@ -104,11 +103,11 @@ def native_eligible(flat, gflat=None) -> bool:
     buffers of the same kind)."""
     if not flat or len(flat) > MAX_NATIVE_PLANES:
         return False
-    dev = flat[0].device
-    for t in list(flat) + list(gflat or ()):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.device == dev and t.is_contiguous()):
-            return False
-    return all(t.numel() <= 0x7fffffff for t in flat)
+    if not flat[0].is_cuda:
+        return False
+    from diff_gaussian_rasterization import _lib
+    B = _lib.Boundary(flat[0].device)
+    return all(B.ok(t) for t in list(flat) + list(gflat or ())) and all(t.numel() <= 0x7fffffff for t in flat)
 
 
 def plane_terms_torch(t: torch.Tensor, need_grad: bool = True):
@@ -166,18 +165,18 @@ def regularize_planes_torch(planes, weights, grads=None, accumulate: bool = True
 def _native(flat, weights, gflat, accumulate: bool) -> PlaneReg:
     from diff_gaussian_rasterization import _lib
     L = _lib.load()
-    n = len(flat)
+    n, dev = len(flat), flat[0].device
+    B = _lib.Boundary(dev)
     desc = (_lib.PlaneDesc * n)()
     for i, t in enumerate(flat):
         d = desc[i]
-        d.t = t.data_ptr()
-        d.grad = gflat[i].data_ptr() if gflat is not None else None
+        d.t = B.ptr(t, f"plane {i}")
+        d.grad = B.ptr(gflat[i], f"gradient {i}") if gflat is not None else None
         _, d.C, d.H, d.W = t.shape
         d.w_smooth, d.w_l1 = plane_weights(weights, i % 6)
     nbytes = int(L.lsr_plane_reg_workspace_bytes(n, desc))
     if nbytes < 0:
         raise ValueError(L.lsr_last_error().decode())
-    dev = flat[0].device
     nbytes = (nbytes + 15) // 16 * 16
     # one allocation: the workspace, then terms [n, 2] float64, total64, total
     buf = torch.empty(nbytes + 16 * n + 16, dtype=torch.uint8, device=dev)
@@ -185,9 +184,9 @@ def _native(flat, weights, gflat, accumulate: bool) -> PlaneReg:
     total64 = buf[nbytes + 16 * n:nbytes + 16 * n + 8].view(torch.float64)
     total = buf[nbytes + 16 * n + 8:nbytes + 16 * n + 12].view(torch.float32)
     with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(L.lsr_plane_reg(n, desc, int(bool(accumulate)), buf.data_ptr(), terms.data_ptr(), total.data_ptr(),
-                                   total64.data_ptr(), st), "lsr_plane_reg")
+        _lib.check(L.lsr_plane_reg(n, desc, int(bool(accumulate)), B.ptr(buf, "workspace", torch.uint8),
+                                   B.ptr(terms, "terms", torch.float64), B.ptr(total, "total"),
+                                   B.ptr(total64, "total64", torch.float64), B.stream()), "lsr_plane_reg")
     return PlaneReg(total.view(()), terms, total64.view(()))
 
 

@@ -4,8 +4,6 @@ distCUDA2(points [P, 3] float32 on the GPU) -> [P] float32: the mean of the squa
 from each point to its 3 nearest other points (scene/gaussian_model.py:203 clamps it at 1e-7 and
 takes log(sqrt(.)) as the initial scale).  Exact 3-NN; GPU only (no CPU fallback).
 """
-import ctypes
-
 import torch
 
 from diff_gaussian_rasterization import _lib
@@ -23,7 +21,7 @@ def distCUDA2(points: torch.Tensor) -> torch.Tensor:
     if P == 0:
         return out
     ws = torch.empty(int(L.lsr_knn_workspace_bytes(P)), dtype=torch.uint8, device=pts.device)
-    stream = torch.cuda.current_stream(pts.device).cuda_stream
-    _lib.check(L.lsr_knn_mean_dist(P, ctypes.c_void_p(pts.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                   ctypes.c_void_p(ws.data_ptr()), ctypes.c_void_p(stream)), "lsr_knn_mean_dist")
+    B = _lib.Boundary(pts.device)
+    _lib.check(L.lsr_knn_mean_dist(P, B.ptr(pts, "points"), B.ptr(out, "out"), B.ptr(ws, "workspace", torch.uint8),
+                                   B.stream()), "lsr_knn_mean_dist")
     return out

@@ -44,8 +44,6 @@ from __future__ import annotations
 
 from typing import Callable, Optional, Sequence
 
-import ctypes
-
 import torch
 
 from gaussian_scene import GaussianScene, render, render_views
@@ -60,41 +58,50 @@ class _L1Views(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gts3, *images):
         from diff_gaussian_rasterization import _lib
-        L = _lib.load()
-        V = len(images)
-        imgs = [x.contiguous() for x in images]
-        n = imgs[0].numel()
-        if gts3.shape[0] != V or any(x.shape != imgs[0].shape or x.dtype != torch.float32 for x in imgs) \
-                or tuple(gts3.shape[1:]) != tuple(imgs[0].shape) or gts3[0].stride() != imgs[0].stride():
+        V, shape = len(images), images[0].shape
+        B = _lib.Boundary(images[0].device)
+        if not _l1_native(B, images, gts3):
+            raise ValueError("l1 loss: up to 8 contiguous float32 CUDA images and gts[:, :3] on their device, "
+                             "float32, its per-view slices contiguous, without a gradient")
+        if gts3.shape[0] != V or any(x.shape != shape for x in images) or tuple(gts3.shape[1:]) != tuple(shape):
             raise ValueError("l1 loss: V float32 images of one shape and gts[:, :3] of that shape")
-        ptrs = (ctypes.c_void_p * V)(*[x.data_ptr() for x in imgs])
-        ws = torch.empty(int(L.lsr_l1_workspace_bytes(V)), dtype=torch.uint8, device=imgs[0].device)
-        loss = torch.empty((), device=imgs[0].device)
-        st = torch.cuda.current_stream(imgs[0].device).cuda_stream
-        _lib.check(L.lsr_l1_loss_views(V, n, ptrs, gts3.data_ptr(), gts3.stride(0), loss.data_ptr(), ws.data_ptr(), st),
-                   "lsr_l1_loss_views")
-        ctx.save_for_backward(gts3, *imgs)
+        L = _lib.load()
+        ws = torch.empty(int(L.lsr_l1_workspace_bytes(V)), dtype=torch.uint8, device=B.device)
+        loss = torch.empty((), device=B.device)
+        _lib.check(L.lsr_l1_loss_views(V, images[0].numel(), B.array(images, "images"), B.ptr(gts3[0], "gts"),
+                                       gts3.stride(0), B.ptr(loss, "loss"), B.ptr(ws, "workspace", torch.uint8),
+                                       B.stream()), "lsr_l1_loss_views")
+        ctx.save_for_backward(gts3, *images)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         from diff_gaussian_rasterization import _lib
         gts3, *imgs = ctx.saved_tensors
-        V = len(imgs)
+        B = _lib.Boundary(imgs[0].device)
         grads = [torch.empty_like(x) for x in imgs]
         g = g.contiguous()
-        st = torch.cuda.current_stream(g.device).cuda_stream
         _lib.check(_lib.load().lsr_l1_loss_views_backward(
-            V, imgs[0].numel(), (ctypes.c_void_p * V)(*[x.data_ptr() for x in imgs]), gts3.data_ptr(), gts3.stride(0),
-            g.data_ptr(), (ctypes.c_void_p * V)(*[x.data_ptr() for x in grads]), st), "lsr_l1_loss_views_backward")
+            len(imgs), imgs[0].numel(), B.array(imgs, "images"), B.ptr(gts3[0], "gts"), gts3.stride(0),
+            B.ptr(g, "grad"), B.array(grads, "grads"), B.stream()), "lsr_l1_loss_views_backward")
         return (None,) + tuple(grads)
+
+
+def _l1_native(B, images, gts3) -> bool:
+    """Whether lsr_l1_loss_views may read these: every image and a view's slice of gts[:, :3] (the views share
+    dtype, device and strides, so the first stands for all) pass the boundary on a CUDA device, and gts wants no
+    gradient (the kernel has none for it)."""
+    return (B.device.type == "cuda" and 1 <= len(images) <= 8 and isinstance(gts3, torch.Tensor)
+            and not gts3.requires_grad and gts3.dim() == images[0].dim() + 1 and gts3.shape[0] == len(images)
+            and all(B.ok(x) for x in images) and B.ok(gts3[0]))
 
 
 def l1_loss_views(images, gts):
     """mean |stack(images) - gts[:, :3]| with its gradient (the base stages' loss); native on the GPU
-    for up to 8 views, PyTorch otherwise."""
+    for up to 8 views when _l1_native(), PyTorch otherwise."""
+    from diff_gaussian_rasterization import _lib
     gts3 = gts[:, :3]
-    if images[0].is_cuda and 1 <= len(images) <= 8 and gts3[0].is_contiguous():
+    if _l1_native(_lib.Boundary(images[0].device), images, gts3):
         return _L1Views.apply(gts3, *images)
     return (torch.stack(images) - gts3).abs().mean()
 

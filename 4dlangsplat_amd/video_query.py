@@ -39,10 +39,10 @@ ROW_TILE = _lib.VIDEO_ROW_TILE      # rows of one block of the layer kernel (LSR
 def native_ok(decoder):
     """The decoder is inside include/lsr_video.h's limits, float32, on one CUDA device."""
     d = decoder.dims
-    ts = decoder.weights + decoder.biases
+    B = _lib.Boundary(decoder.device)
     return (len(decoder.weights) <= _lib.QUERY_MAX_LAYERS and 1 <= d[0] <= _lib.QUERY_MAX_INPUT
             and all(x % 16 == 0 and 16 <= x <= _lib.VIDEO_MAX_WIDTH for x in d[1:])
-            and all(t.dtype == torch.float32 and t.device.type == "cuda" and t.device == ts[0].device for t in ts))
+            and decoder.device.type == "cuda" and all(B.ok(t) for t in decoder.weights + decoder.biases))
 
 
 def _unit_queries(queries, d_out):
@@ -68,7 +68,7 @@ def _cosine_native(rows, decoder, qn, chunk_rows):
     out = torch.empty(n_q, n, dtype=torch.float32, device=dev)
     if n == 0:
         return out
-    lib, dec = _lib.load(), decoder._struct()
+    lib, dec, B = _lib.load(), decoder._struct(), _lib.Boundary(dev)
     step = min(n, chunk_rows)
     ws_bytes = lib.lsr_video_workspace_bytes(ctypes.byref(dec), step)
     if ws_bytes < 0:
@@ -76,11 +76,12 @@ def _cosine_native(rows, decoder, qn, chunk_rows):
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     part = out if step == n else torch.empty(n_q * step, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = B.stream()
         for r0 in range(0, n, step):
             m = min(step, n - r0)
-            _lib.check(lib.lsr_video_cosine(ctypes.byref(dec), m, rows[r0:].data_ptr(), n_q, qn.data_ptr(),
-                                            part.data_ptr(), ws.data_ptr(), ws_bytes, stream), "lsr_video_cosine")
+            _lib.check(lib.lsr_video_cosine(ctypes.byref(dec), m, B.ptr(rows[r0:], "rows"), n_q, B.ptr(qn, "queries"),
+                                            B.ptr(part, "out"), B.ptr(ws, "workspace", torch.uint8), ws_bytes, stream),
+                       "lsr_video_cosine")
             if part is not out:
                 out[:, r0:r0 + m] = part[:n_q * m].view(n_q, m)
     return out
@@ -175,10 +176,12 @@ def masked_similarity(latent, masks, decoder, queries, layout="hwc", chunk_rows=
             cos = _cosine_native(rows, decoder, q32[pick].contiguous(), int(chunk_rows))
             offs = torch.tensor(np.concatenate([[0], np.cumsum(n[k0:k1])]), dtype=torch.int64, device=x.device)
             sq = torch.tensor(seg_q, dtype=torch.int32, device=x.device)
+            B = _lib.Boundary(x.device)
             with torch.cuda.device(x.device):
-                _lib.check(lib.lsr_video_segment_mean(total, len(pick), cos.data_ptr(), k1 - k0, offs.data_ptr(),
-                                                      sq.data_ptr(), sims[k0:k1].data_ptr(),
-                                                      torch.cuda.current_stream(x.device).cuda_stream),
+                _lib.check(lib.lsr_video_segment_mean(total, len(pick), B.ptr(cos, "cosines"), k1 - k0,
+                                                      B.ptr(offs, "offsets", torch.int64),
+                                                      B.ptr(sq, "query slots", torch.int32),
+                                                      B.ptr(sims[k0:k1], "sims"), B.stream()),
                            "lsr_video_segment_mean")
         k0 = k1
     return sims, counts

@@ -837,13 +837,11 @@ class ShardedAdam:
         if self._adam is not None:
             self._adam(p, g, m, v, lr, step)
             return
-        import ctypes
-
         from diff_gaussian_rasterization import _lib
-        L = _lib.load()
+        L, B = _lib.load(), _lib.Boundary(p.device)
         ag = _lib.AdamGroup()
-        ag.param, ag.grad, ag.exp_avg, ag.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
+        ag.param, ag.grad = B.ptr(p, "param"), B.ptr(g, "grad")
+        ag.exp_avg, ag.exp_avg_sq = B.ptr(m, "exp_avg"), B.ptr(v, "exp_avg_sq")
         ag.n, ag.lr, ag.step = p.numel(), float(lr), int(step)
         arr = (_lib.AdamGroup * 1)(ag)
-        _lib.check(L.lsr_adam_step(arr, 1, self.betas[0], self.betas[1], self.eps,
-                                   ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)), "lsr_adam_step")
+        _lib.check(L.lsr_adam_step(arr, 1, self.betas[0], self.betas[1], self.eps, B.stream()), "lsr_adam_step")

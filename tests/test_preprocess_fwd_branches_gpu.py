@@ -181,7 +181,7 @@ def _phase1(variant, nv, chunks=None):
         n = len(cams)
         host = torch.zeros(n, 2, dtype=torch.int32, pin_memory=True)
         s_arr, o_arr = dgr._settings_array(sts), dgr._struct_array(dgr._lib.FwdOut, fouts)
-        g_arr = dgr._ptr_array(geoms)
+        g_arr = dgr._lib.Boundary(geoms[0].device).array(geoms, "geom", torch.uint8)
         if chunks is None:
             dgr._lib.check(L.lsr_forward_preprocess_views_async(n, s_arr, ctypes.byref(fin), o_arr, g_arr,
                                                                 ctypes.c_void_p(host.data_ptr()), stp),
